@@ -6,6 +6,11 @@ Contract (driver): ``python bench.py --gpus N --steps K --warmup W``; for N > 1 
 JSON line.  Workload = BASELINE.json configs[1]: ViT-B/16 + AIM, 8 frames 224^2, bf16 operands / fp32
 accumulate, 64 clips per GPU, synthetic N(0,1) clips and U{0..399} labels, random-init weights
 (pretrained=None, D_fc2 ~ N(0, .02) so the adapters are live), drop_path 0.2 and head dropout 0.5 ON.
+
+A plain run sets up, warms up, times ``--steps`` steps and prints the line (``roofline``, ``secondary``, ``inference``
+and ``cpu_baseline`` are null in it).  ``--full`` adds those four measurements after the timed steps.
+``--dump-outputs DIR`` writes what the last timed step computed (``dump_outputs``); the inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -35,10 +40,15 @@ def parse():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=64, help="clips per GPU")
     ap.add_argument("--frames", type=int, default=8)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the ViT-L/14 16-frame block (BASELINE configs[3] shape)")
-    ap.add_argument("--no-inference", action="store_true", help="skip the fp8 multi-view inference block (BASELINE configs[4] shape)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the per-kernel GEMM roofline, the ViT-L/14 "
+                         "training and fp8 inference blocks and the CPU baseline (each can be dropped with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="with --full: skip the per-kernel GEMM timing (roofline)")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the ViT-L/14 16-frame block (BASELINE configs[3] shape)")
+    ap.add_argument("--no-inference", action="store_true", help="with --full: skip the fp8 multi-view inference block (BASELINE configs[4] shape)")
     ap.add_argument("--inference-only", action="store_true", help="profiling aid: run only the inference block and print it")
     ap.add_argument("--secondary-only", action="store_true", help="profiling aid: run only the ViT-L/14 training block and print it")
     return ap.parse_args()
@@ -230,6 +240,23 @@ def inference_l14(dev, rank, world, samples=4, views=3, frames=32, steps=4, warm
             "peak_mem_gib": round(torch.cuda.max_memory_allocated(dev) / 2 ** 30, 1)}
 
 
+def dump_outputs(out_dir, model, losses, grad_samples=1 << 21, seed=0):
+    """``--dump-outputs``: what the last timed step handed its caller, as .npy files (about 52 MB for ViT-B/16):
+    each entry of the loss dict (float64), every trainable parameter after the AdamW update, flattened and concatenated
+    in ``named_parameters()`` order (``params.npy``, float32), and the gradient over the same flat order at
+    ``grad_samples`` positions drawn by ``torch.randperm`` seeded with ``seed``, ascending (``grads_sample.npy``, float32)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in losses.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), torch.as_tensor(v).detach().double().cpu().numpy())
+    train = [p for _, p in model.named_parameters() if p.requires_grad]
+    flat_p = torch.cat([p.detach().reshape(-1) for p in train]).float().cpu()
+    flat_g = torch.cat([p.grad.detach().reshape(-1) for p in train]).float().cpu()
+    idx = torch.randperm(flat_g.numel(), generator=torch.Generator().manual_seed(seed))[:grad_samples].sort().values
+    np.save(os.path.join(out_dir, "params.npy"), flat_p.numpy())
+    np.save(os.path.join(out_dir, "grads_sample.npy"), flat_g[idx].numpy())
+
+
 def main():
     args = parse()
     from aim_amd.dist import broadcast_module, build_optimizer, init_distributed
@@ -280,7 +307,7 @@ def main():
     for _ in range(args.warmup):
         step()
     fence()
-    timing = (not args.no_kernel_timing) and rank == 0
+    timing = args.full and (not args.no_kernel_timing) and rank == 0
     if timing:
         ops.GEMM_TIMER.start()
     t0 = time.perf_counter()
@@ -294,6 +321,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
     loss_val = float(losses["loss_cls"].detach())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, losses)
     if os.environ.get("AIM_JOIN_STATS") and rank == 0:
         from aim_amd import backbone as _bb
         print("join stalls, ms per step:", {k: round(v / (args.steps + args.warmup), 3) for k, v in _bb.join_stats().items()}, file=sys.stderr)
@@ -358,7 +387,7 @@ def main():
     sec = None
     del model, opt, imgs, label, losses
     torch.cuda.empty_cache()
-    if not args.no_secondary and args.frames == 8:
+    if args.full and not args.no_secondary and args.frames == 8:
         torch.cuda.reset_peak_memory_stats(dev)
         try:
             sec = secondary_l14(dev, rank, world)
@@ -368,7 +397,7 @@ def main():
             sec = {"error": repr(e)[:300]}
         torch.cuda.empty_cache()
     inf = None
-    if not args.no_inference and args.frames == 8:
+    if args.full and not args.no_inference and args.frames == 8:
         torch.cuda.reset_peak_memory_stats(dev)
         try:
             inf = inference_l14(dev, rank, world)
@@ -380,7 +409,7 @@ def main():
     if rank == 0:
         out["secondary"] = sec
         out["inference"] = inf
-        out["cpu_baseline"] = None if (args.no_cpu_baseline or world > 1) else cpu_baseline(args.frames)
+        out["cpu_baseline"] = None if (not args.full or args.no_cpu_baseline or world > 1) else cpu_baseline(args.frames)
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

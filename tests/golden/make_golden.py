@@ -282,8 +282,49 @@ def gen_cfg1(mod, seed):
     np.savez_compressed(os.path.join(HERE, "backbone_cfg1.npz"), **npify(out))
 
 
+CFG_KEYS = ("_base_", "model", "optimizer", "optimizer_config", "module_hooks")
+
+
+def _cfg_data(o):
+    """JSON form of a config value; tuples are tagged so the test rebuilds them as tuples."""
+    if isinstance(o, dict):
+        return {k: _cfg_data(v) for k, v in o.items()}
+    if isinstance(o, tuple):
+        return {"__tuple__": [_cfg_data(v) for v in o]}
+    if isinstance(o, list):
+        return [_cfg_data(v) for v in o]
+    return o
+
+
+def gen_configs():
+    """reference_vit_configs.json: the values of the keys tests/test_reference_configs.py reads (CFG_KEYS) from every
+    configs/recognition/vit/vitclip_*.py of the reference and each ``_base_`` file they inherit, by path under configs/."""
+    import glob
+    import json
+    from aim_amd.registry import _load_py
+    cfg_root = os.path.join(REF.split("/mmaction/")[0], "configs")
+    todo = sorted(glob.glob(os.path.join(cfg_root, "recognition", "vit", "vitclip_*.py")))
+    out = {}
+    while todo:
+        path = os.path.normpath(todo.pop(0))
+        rel = os.path.relpath(path, cfg_root)
+        if rel in out:
+            continue
+        d = {k: v for k, v in _load_py(path).items() if k in CFG_KEYS}
+        out[rel] = _cfg_data(d)
+        bases = d.get("_base_", [])
+        todo += [os.path.join(os.path.dirname(path), b) for b in ([bases] if isinstance(bases, str) else bases)]
+    with open(os.path.join(HERE, "reference_vit_configs.json"), "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+
+
 def main():
     torch.set_num_threads(8)
+    if "--configs-only" in sys.argv:        # the config fixtures of tests/test_reference_configs.py
+        import aim_amd  # noqa: F401
+        gen_configs()
+        return
     mod = load_reference()
     if "--aim-only" in sys.argv:            # stock-AIM variant (vitclip_aim.py), round 2
         aim = load_reference_aim()

@@ -2,37 +2,63 @@
 ``aim_amd.Config.fromfile`` (``_base_`` inheritance included) and ``aim_amd.build_model`` UNCHANGED, and the model that
 comes out has the reference's architecture numbers, freeze policy and state_dict keys.
 
-The config files are read where they lie under ``/root/reference`` (nothing is copied into this repository); on a box
-without the reference (the GPU box) the whole module is skipped.  Two configs cannot build, and must fail the way the
-reference itself does:
+The configs are stored as data: ``tests/golden/reference_vit_configs.json`` holds, for each of the nine files and the
+``_base_`` files they inherit, the values of the keys read here (``_base_``, ``model``, ``optimizer``,
+``optimizer_config``, ``module_hooks``), keyed by path under ``configs/`` (``tests/golden/make_golden.py
+--configs-only``).  Each test writes them back as config files under the same relative paths, so loading goes through
+``Config.fromfile`` and its ``_base_`` merge as it does on the reference tree.  Two configs cannot build, and must fail
+the way the reference itself does:
 
 * ``vitclip_base_hmdb51.py``: ``pretrained='openaiclip'`` -> ``clip.load`` (vit_clip.py:369-372); the ``clip`` package
   and its downloaded weights are absent here, so ``init_weights`` raises the documented ``RuntimeError``;
 * ``vitclip_base_sthv2.py`` passes ``num_tadapter=2``, a keyword the reference's own ``ViT_CLIP.__init__``
   (vit_clip.py:330-331) does not take: ``TypeError`` there and here.
 """
-import glob
+import json
 import os
 
 import pytest
 import torch
 
-REF_CFG = "/root/reference/configs/recognition/vit"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF_CFG), reason="reference tree not present on this box")
+HERE = os.path.dirname(os.path.abspath(__file__))
+with open(os.path.join(HERE, "golden", "reference_vit_configs.json")) as _f:
+    CONFIGS = json.load(_f)
 
-FILES = sorted(glob.glob(os.path.join(REF_CFG, "vitclip_*.py")))
+FILES = sorted(p for p in CONFIGS if p.startswith("recognition/vit/vitclip_"))
 ARCH = {"base": dict(width=768, layers=12, heads=12, patch_size=16, tokens=197),
         "large": dict(width=1024, layers=24, heads=16, patch_size=14, tokens=257)}
 KNOWN_FAIL = {"vitclip_base_hmdb51.py": (RuntimeError, "clip"), "vitclip_base_sthv2.py": (TypeError, "num_tadapter")}
+
+
+def _value(o):
+    if isinstance(o, dict):
+        if set(o) == {"__tuple__"}:
+            return tuple(_value(v) for v in o["__tuple__"])
+        return {k: _value(v) for k, v in o.items()}
+    if isinstance(o, list):
+        return [_value(v) for v in o]
+    return o
+
+
+def _write_config_tree(root):
+    """Every stored config file as ``key = <literal>`` lines under ``root``, at its path under configs/."""
+    for rel, d in CONFIGS.items():
+        path = os.path.join(root, rel)
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        with open(path, "w") as f:
+            for k, v in d.items():
+                f.write(f"{k} = {_value(v)!r}\n")
 
 
 def test_the_nine_configs_are_there():
     assert len(FILES) == 9 and set(KNOWN_FAIL) <= {os.path.basename(f) for f in FILES}
 
 
-@pytest.mark.parametrize("path", FILES, ids=[os.path.basename(f) for f in FILES])
-def test_reference_config_builds_unchanged(path):
+@pytest.mark.parametrize("rel", FILES, ids=[os.path.basename(f) for f in FILES])
+def test_reference_config_builds_unchanged(rel, tmp_path):
     import aim_amd
+    _write_config_tree(str(tmp_path))
+    path = os.path.join(str(tmp_path), rel)
     name = os.path.basename(path)
     cfg = aim_amd.Config.fromfile(path)
     m = cfg.model
