@@ -12,7 +12,7 @@ from .lib import load_library, library_path, LibraryNotBuilt  # noqa: F401
 
 __all__ = ["load_library", "library_path", "LibraryNotBuilt"]
 
-from .registry import (BACKBONES, HEADS, LOSSES, MODELS, RECOGNIZERS, Config, Registry,  # noqa: E402,F401
+from .registry import (BACKBONES, BLENDINGS, HEADS, LOSSES, MODELS, RECOGNIZERS, Config, Registry,  # noqa: E402,F401
                        build_backbone, build_from_cfg, build_head, build_loss, build_model, build_recognizer,
                        register_into_mmaction)
 from .backbone import ViT_CLIP  # noqa: E402,F401
@@ -20,9 +20,10 @@ from .aim_variant import AIM  # noqa: E402,F401
 from .recognizer import (CrossEntropyLoss, GPUNormalize, I3DHead, Recognizer3D,  # noqa: E402,F401
                          register_module_hooks, top_k_accuracy)
 
+from .blending import CutmixBlending, LabelSmoothing, MixupBlending  # noqa: E402,F401
 from .dist import DistOptimizerHook, FlatAdamW, build_optimizer  # noqa: E402,F401
 
 __all__ += ["DistOptimizerHook", "FlatAdamW", "build_optimizer", "BACKBONES", "HEADS", "LOSSES", "MODELS", "RECOGNIZERS", "Config", "Registry", "build_backbone",
             "build_from_cfg", "build_head", "build_loss", "build_model", "build_recognizer", "register_into_mmaction",
             "ViT_CLIP", "AIM", "Recognizer3D", "I3DHead", "CrossEntropyLoss", "GPUNormalize", "register_module_hooks",
-            "top_k_accuracy"]
+            "top_k_accuracy", "BLENDINGS", "LabelSmoothing", "MixupBlending", "CutmixBlending"]

@@ -788,7 +788,11 @@ class _BackboneFn(torch.autograd.Function):
         # patch embedding as a GEMM (conv1: kernel = stride = patch, no bias; vit_clip.py:436)
         Kp = frozen["conv"].shape[1]
         A = _empty((BT * G * G, Kp), BF16, dev)
-        ops.patchify(imgs, A, B, T, Hh, Ww, p, Kp, *model._norm_now)
+        blend, model._blend_now = model._blend_now, None
+        if blend is not None:    # Mixup / Cutmix applied while gathering: the blended clip batch is never written
+            ops.patchify_blend(imgs, A, B, T, Hh, Ww, p, Kp, *model._norm_now, blend=blend)
+        else:
+            ops.patchify(imgs, A, B, T, Hh, Ww, p, Kp, *model._norm_now)
         tok = _empty((BT * G * G, D), BF16, dev)
         ops.gemm(A, frozen["conv"], ops.EPI_BF16, tok)
         del A
@@ -959,6 +963,8 @@ class ViT_CLIP(nn.Module):
         self._frozen_cache = None
         self._norm_mean = self._norm_std = None     # set by a fused GPUNormalize hook (module_hooks.py) for the NEXT forward only
         self._norm_now = (None, None)               # what this forward's patch gather applies
+        self._blend_next = None                     # a fused Mixup / Cutmix (blending.FusedBlend) armed by Recognizer3D for the NEXT forward only
+        self._blend_now = None                      # what this forward's patch gather applies
         self.grad_in_place = False                  # accumulate straight into param.grad (see _BackboneFn.backward)
         self.grad_ready_hook = None                 # fn(layer, in_place, streams): set by dist.FlatAdamW (overlapped all-reduce)
         self._fp8_cache = None
@@ -1160,6 +1166,7 @@ class ViT_CLIP(nn.Module):
 
     # ---- forward --------------------------------------------------------------------------------
     def forward(self, x: torch.Tensor):
+        blend, self._blend_next = self._blend_next, None
         if not x.is_cuda:
             raise RuntimeError("aim_amd.ViT_CLIP runs on MI355X only (HIP kernels); there is no CPU fallback")
         B, C, T, H, W = x.shape
@@ -1176,6 +1183,10 @@ class ViT_CLIP(nn.Module):
         self._norm_mean = self._norm_std = None
         if x.dtype == torch.uint8 and self._norm_now[0] is None:
             raise TypeError("uint8 clips need a GPUNormalize module hook on the backbone (module_hooks.py:35-87)")
+        if blend is not None and (x.dtype not in (torch.float32, torch.uint8) or blend.partner.numel() != B):
+            raise TypeError(f"a fused blending needs float32 or uint8 clips and one partner per clip, got {x.dtype} and "
+                            f"{blend.partner.numel()} partners for {B} clips")
+        self._blend_now = blend
         if self.precision == 'fp32':
             from .fp32_path import _BackboneFn32, forward_f32
             if torch.is_grad_enabled() and any(p.requires_grad for p in self._trainable_list()):

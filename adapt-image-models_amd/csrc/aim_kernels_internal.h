@@ -18,6 +18,8 @@ int aim_gemm_small_launch(const GemmArgs& g, int epi, int batch, hipStream_t st)
 int aim_gemm_small_fp8_launch(const GemmArgs& g, int epi, hipStream_t st);
 // rows of a thin last tile round that go to the small-tile kernel (0: no peel); fills M0 = rows of the whole rounds
 int aim_gemm_peel_rows(const GemmArgs& g, int* M0);
+// argument checks of the fused-blend patch gathers (embed_misc.hip); nonzero: the error is set
+int aim_blend_check(const char* who, const int* partner, int mode, int H, int W, int x1, int y1, int x2, int y2);
 // EXPSUM problems of one 256x256 tile per batch item run on the persistent kernel (8 partial slots per item)
 static inline bool aim_expsum_use256(int M, int N) {
     static const bool on = [] { const char* e = getenv("AIM_EXPSUM_256"); return !e || atoi(e) != 0; }();

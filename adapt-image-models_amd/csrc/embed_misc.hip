@@ -80,6 +80,108 @@ __global__ __launch_bounds__(256) void patchify_kernel(const TIN* __restrict__ i
     *(bf16x8*)(A + row * Kp + k0) = o;
 }
 
+// 8 consecutive pixels of one image row (16-byte aligned) -> f32
+template <typename TIN>
+__device__ __forceinline__ void load_px8(const TIN* src, float v[8]) {
+    if constexpr (sizeof(TIN) == 4) {
+        const f32x4 a0 = *(const f32x4*)src, a1 = *(const f32x4*)(src + 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            v[e] = a0[e];
+            v[4 + e] = a1[e];
+        }
+    } else {
+        const uint2 a0 = *(const uint2*)src;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            v[e] = (float)((a0.x >> (8 * e)) & 0xffu);
+            v[4 + e] = (float)((a0.y >> (8 * e)) & 0xffu);
+        }
+    }
+}
+
+// patchify_kernel with a mixup / cutmix of two clips applied while gathering (AimBlend): the blended clip is never
+// written.  Mixup blends the NORMALISED values when the uint8 GPUNormalize is fused (lam * norm(a) + oml * norm(b)).
+template <typename TIN>
+__global__ __launch_bounds__(256) void patchify_blend_kernel(const TIN* __restrict__ img, const float* __restrict__ mean3,
+                                                             const float* __restrict__ std3, bf16_t* __restrict__ A, int B,
+                                                             int T, int H, int W, int p, int Kp, AimBlend bl) {
+    const int G = W / p, Gy = H / p, K = 3 * p * p;
+    const long long rows = (long long)B * T * Gy * G;
+    const int cpr = Kp / 8;
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= rows * cpr) return;
+    const long long row = idx / cpr;
+    const int k0 = (int)(idx - row * cpr) * 8;
+    const int gx = (int)(row % G), gy = (int)((row / G) % Gy);
+    const long long bt = row / ((long long)G * Gy);
+    const int t = (int)(bt % T);
+    const long long b = bt / T, pb = blend_partner(bl, b, B);
+    const bool mixup = bl.mode == 1;
+    bf16x8 o;
+    if ((p & 7) == 0 && (W & 7) == 0 && k0 + 8 <= K && ((unsigned long long)img & 15) == 0) {
+        // 8 consecutive pixels of one image row, as in patchify_kernel.  Cutmix loads the partner's run only where the box
+        // covers it: a run outside the box reads clip b, a run inside it clip partner[b], a run across an edge both.
+        const int c = k0 / (p * p), rem = k0 - c * p * p, py = rem / p, px = rem - py * p;
+        const int y = gy * p + py, x0 = gx * p + px;
+        const long long pix = ((long long)t * H + y) * W + x0;
+        const TIN* sa = img + (b * 3 + c) * (long long)T * H * W + pix;
+        const TIN* sb = img + (pb * 3 + c) * (long long)T * H * W + pix;
+        const bool rowin = y >= bl.y1 && y < bl.y2;
+        const bool none = !mixup && (!rowin || x0 + 8 <= bl.x1 || x0 >= bl.x2);
+        const bool all = !mixup && rowin && x0 >= bl.x1 && x0 + 8 <= bl.x2;
+        float va[8] = {}, vb[8] = {};
+        if (!all) load_px8(sa, va);
+        if (!none) load_px8(sb, vb);
+        if (mean3) {
+            const float m = mean3[c], sd = std3[c];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                va[e] = (va[e] - m) / sd;
+                vb[e] = (vb[e] - m) / sd;
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            float v;
+            if (mixup)
+                v = blend_mix(va[e], vb[e], bl.lam, bl.oml);
+            else if (none)
+                v = va[e];
+            else if (all)
+                v = vb[e];
+            else
+                v = (x0 + e >= bl.x1 && x0 + e < bl.x2) ? vb[e] : va[e];
+            o[e] = (bf16_t)v;
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int k = k0 + e;
+            float v = 0.f;
+            if (k < K) {
+                const int c = k / (p * p), rem = k - c * p * p, py = rem / p, px = rem - py * p;
+                const int y = gy * p + py, x = gx * p + px;
+                const long long pix = ((long long)t * H + y) * W + x;
+                const long long sa = (b * 3 + c) * (long long)T * H * W + pix, sb = (pb * 3 + c) * (long long)T * H * W + pix;
+                if (mixup) {
+                    float a = (float)img[sa], q = (float)img[sb];
+                    if (mean3) {
+                        a = (a - mean3[c]) / std3[c];
+                        q = (q - mean3[c]) / std3[c];
+                    }
+                    v = blend_mix(a, q, bl.lam, bl.oml);
+                } else {
+                    v = (float)img[blend_in_box(bl, y, x) ? sb : sa];
+                    if (mean3) v = (v - mean3[c]) / std3[c];
+                }
+            }
+            o[e] = (bf16_t)v;
+        }
+    }
+    *(bf16x8*)(A + row * Kp + k0) = o;
+}
+
 __device__ __forceinline__ f32x4 embed_value(const bf16_t* tok, const float* cls, const float* pos, const float* tmp,
                                              long long bt, int n, int t, int G2, int D, int c4) {
     f32x4 v;
@@ -709,5 +811,39 @@ extern "C" int aim_scale_rows(const float* x, const float* s, aim_bf16* y, float
     hipLaunchKernelGGL(scale_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, s,
                        (bf16_t*)y, y_f32, R, C);
     AIM_CHECK_LAUNCH("aim_scale_rows");
+    return 0;
+}
+
+// shared by aim_patchify_blend and aim_patchify_blend_f32 (fp32.hip)
+int aim_blend_check(const char* who, const int* partner, int mode, int H, int W, int x1, int y1, int x2, int y2) {
+    AIM_CHECK_ARG(partner, "%s: partner is NULL", who);
+    AIM_CHECK_ARG(mode == 1 || mode == 2, "%s: mode must be 1 (mixup) or 2 (cutmix), got %d", who, mode);
+    AIM_CHECK_ARG(mode == 1 || (0 <= x1 && x1 <= x2 && x2 <= W && 0 <= y1 && y1 <= y2 && y2 <= H),
+                  "%s: box x [%d, %d) y [%d, %d) outside the %d x %d image", who, x1, x2, y1, y2, W, H);
+    return 0;
+}
+
+extern "C" int aim_patchify_blend(const void* imgs, int in_dtype, const float* mean3, const float* std3, aim_bf16* A, int B,
+                                  int T, int H, int W, int p, int Kp, const int* partner, int mode, float lam, float oml,
+                                  int x1, int y1, int x2, int y2, void* stream) {
+    AIM_CHECK_ARG(B > 0 && T > 0 && p > 0 && H % p == 0 && W % p == 0, "patchify_blend: bad shape H=%d W=%d p=%d", H, W, p);
+    AIM_CHECK_ARG(Kp >= 3 * p * p && (Kp % 8) == 0, "patchify_blend: Kp=%d must be >= 3*p*p and a multiple of 8", Kp);
+    AIM_CHECK_ARG(imgs && A && ((!mean3) == (!std3)), "patchify_blend: null pointer");
+    if (aim_blend_check("patchify_blend", partner, mode, H, W, x1, y1, x2, y2)) return 1;
+    const AimBlend bl{partner, mode, lam, oml, x1, y1, x2, y2};
+    const long long total = (long long)B * T * (H / p) * (W / p) * (Kp / 8);
+    const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    if (in_dtype == 0)
+        hipLaunchKernelGGL(patchify_blend_kernel<float>, grid, block, 0, st, (const float*)imgs, mean3, std3, (bf16_t*)A, B, T, H,
+                           W, p, Kp, bl);
+    else if (in_dtype == 1)
+        hipLaunchKernelGGL(patchify_blend_kernel<uint8_t>, grid, block, 0, st, (const uint8_t*)imgs, mean3, std3, (bf16_t*)A, B, T,
+                           H, W, p, Kp, bl);
+    else {
+        aim_set_error("patchify_blend: in_dtype must be 0 (f32) or 1 (uint8), got %d", in_dtype);
+        return 1;
+    }
+    AIM_CHECK_LAUNCH("aim_patchify_blend");
     return 0;
 }

@@ -1,5 +1,5 @@
 // Classification tail right after the backbone: I3DHead (avg-pool over frames, dropout, fc_cls), hard-label
-// cross-entropy and top-k accuracy, forward and backward, on the device.  gfx950 only.
+// cross-entropy and top-k accuracy, soft-label / class-weighted cross-entropy, forward and backward, on the device.  gfx950 only.
 //
 // Replaces: mmaction/models/heads/i3d_head.py:53-73 (AdaptiveAvgPool3d -> Dropout -> Linear),
 // mmaction/models/losses/cross_entropy_loss.py:78 (F.cross_entropy, mean over the batch) and
@@ -105,6 +105,79 @@ __global__ __launch_bounds__(64) void ce_finish_kernel(const float* __restrict__
     }
 }
 
+// soft-label cross-entropy (cross_entropy_loss.py:52-76), per sample b, with w = class_weight (NULL: all ones):
+//   loss_b = sum_c w_c y_bc (lse_b - s_bc)   (= -sum_c w y log_softmax),   wy_b = sum_c w_c y_bc,
+//   dscore row numerator = softmax_b * wy_b - w y_b   (the gradient of loss_b; ce_soft_finish_kernel divides by the denominator).
+// Three strided passes over the row: max; sum exp and wy; the loss terms and the dscore row.  C is any size: the row is strided.
+__global__ __launch_bounds__(256) void ce_soft_kernel(const float* __restrict__ score, const float* __restrict__ label,
+                                                      const float* __restrict__ cw, float* __restrict__ dscore,
+                                                      float* __restrict__ per_sample, int C) {
+    __shared__ float red[8];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* s = score + (long long)b * C;
+    const float* y = label + (long long)b * C;
+    float mx = -INFINITY;
+    for (int c = tid; c < C; c += 256) mx = fmaxf(mx, s[c]);
+    mx = wave_max(mx);
+    if (lane == 0) red[wave] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    __syncthreads();
+    float sum = 0.f, wy = 0.f;                     // sum exp(s - mx), sum w y
+    for (int c = tid; c < C; c += 256) {
+        sum += expf(s[c] - mx);
+        wy += (cw ? cw[c] : 1.f) * y[c];
+    }
+    sum = wave_sum(sum);
+    wy = wave_sum(wy);
+    if (lane == 0) { red[wave] = sum; red[4 + wave] = wy; }
+    __syncthreads();
+    sum = (red[0] + red[1]) + (red[2] + red[3]);
+    wy = (red[4] + red[5]) + (red[6] + red[7]);
+    __syncthreads();
+    const float lse = mx + logf(sum);
+    float loss = 0.f;                              // the terms w y (lse - s) as the reference sums -w y log_softmax
+    for (int c = tid; c < C; c += 256) {
+        const float v = s[c], t = (cw ? cw[c] : 1.f) * y[c];
+        loss += t * (lse - v);
+        if (dscore) dscore[(long long)b * C + c] = expf(v - lse) * wy - t;
+    }
+    loss = wave_sum(loss);
+    if (lane == 0) red[wave] = loss;
+    __syncthreads();
+    if (tid == 0) {
+        per_sample[b * 2 + 0] = (red[0] + red[1]) + (red[2] + red[3]);
+        per_sample[b * 2 + 1] = wy;
+    }
+}
+
+// ordered finish (bitwise reproducible): denom = sum_b wy_b in sample order (weighted) or B (the plain mean); block 0 writes
+// out[0] = sum_b loss_b / denom, and block b (when dscore is wanted) divides dscore row b by the same denom
+__global__ __launch_bounds__(256) void ce_soft_finish_kernel(const float* __restrict__ per_sample, float* __restrict__ dscore,
+                                                             float* __restrict__ out, int B, int C, int weighted) {
+    __shared__ float sden;
+    const int tid = threadIdx.x;
+    if (tid == 0) {
+        float den = 0.f;
+        if (weighted)
+            for (int b = 0; b < B; ++b) den += per_sample[b * 2 + 1];
+        else
+            den = (float)B;
+        sden = den;
+        if (blockIdx.x == 0) {
+            float l = 0.f;
+            for (int b = 0; b < B; ++b) l += per_sample[b * 2 + 0];
+            out[0] = l / den;
+        }
+    }
+    __syncthreads();
+    if (dscore) {
+        const float den = sden;
+        float* row = dscore + (long long)blockIdx.x * C;
+        for (int c = tid; c < C; c += 256) row[c] = row[c] / den;
+    }
+}
+
 // dW[c][d] += sum_b dscore[b][c] pooled[b][d]; db[c] += sum_b dscore[b][c]   (grid: C blocks; fixed summation order)
 __global__ __launch_bounds__(256) void head_wgrad_kernel(const float* __restrict__ dscore, const float* __restrict__ pooled,
                                                          float* __restrict__ dW, float* __restrict__ db, int B, int D, int C) {
@@ -180,5 +253,17 @@ extern "C" int aim_ce_topk(const float* score, const int64_t* label, float* dsco
     AIM_CHECK_LAUNCH("aim_ce_topk");
     hipLaunchKernelGGL(ce_finish_kernel, dim3(1), dim3(64), 0, st, per_sample, out3, B);
     AIM_CHECK_LAUNCH("aim_ce_topk(finish)");
+    return 0;
+}
+
+extern "C" int aim_ce_soft(const float* score, const float* label, const float* class_weight, float* dscore, float* per_sample,
+                           float* out, int B, int C, void* stream) {
+    AIM_CHECK_ARG(score && label && per_sample && out && B > 0 && C > 0, "ce_soft: bad arguments");
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(ce_soft_kernel, dim3(B), dim3(256), 0, st, score, label, class_weight, dscore, per_sample, C);
+    AIM_CHECK_LAUNCH("aim_ce_soft");
+    hipLaunchKernelGGL(ce_soft_finish_kernel, dim3(dscore ? B : 1), dim3(256), 0, st, per_sample, dscore, out, B, C,
+                       class_weight ? 1 : 0);
+    AIM_CHECK_LAUNCH("aim_ce_soft(finish)");
     return 0;
 }

@@ -68,6 +68,7 @@ SIGNATURES = {
     "aim_lambda": [P, P, I, P, P, I, P, P, I, I, I, F, P],
     "aim_qk_border": [P, P, I, P, P, I, I, I, I, I, F, P],
     "aim_patchify": [P, I, P, P, P, I, I, I, I, I, I, P],
+    "aim_patchify_blend": [P, I, P, P, P, I, I, I, I, I, I, P, I, F, F, I, I, I, I, P],
     "aim_embed_ln": [P, P, P, P, P, P, P, P, P, I, I, I, I, F, P],
     "aim_embed_bwd": [P, I, P, P, P, P, P, P, P, P, I, I, I, I, P, L, P],
     "aim_embed_bwd_workspace_bytes": [I, I, I, I],
@@ -80,12 +81,14 @@ SIGNATURES = {
     "aim_head_fwd": [P, P, P, P, P, P, I, I, I, I, P],
     "aim_head_bwd": [P, P, P, P, P, P, P, I, I, I, I, P],
     "aim_ce_topk": [P, P, P, P, P, I, I, I, P],
+    "aim_ce_soft": [P, P, P, P, P, P, I, I, P],
     "aim_cast_multi": [P, I, P],
     "aim_gemm_f32": [POINTER(GemmArgs), I, I, P],
     "aim_attn_fwd_f32": [P, P, I, I, I, P],
     "aim_cls_attn_fwd_f32": [P, L, P, I, I, I, P],
     "aim_lambda_f32": [P, I, P, P, I, P, P, I, I, I, F, P],
     "aim_patchify_f32": [P, I, P, P, P, I, I, I, I, I, I, P],
+    "aim_patchify_blend_f32": [P, I, P, P, P, I, I, I, I, I, I, P, I, F, F, I, I, I, I, P],
     "aim_embed_ln_f32": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, F, P],
     "aim_attn_bwd_f32_workspace_bytes": [I, I, I],
     "aim_attn_bwd_f32": [P, P, P, I, I, I, P, L, P],
@@ -96,7 +99,7 @@ SIGNATURES = {
     "aim_wgrad_f32": [P, I, P, I, P, I, I, I, P, P, I, P, L, P],
 }
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 
 def load_library():

@@ -478,6 +478,20 @@ def head_bwd(dscore, pooled, drop, W, T, need_dfeat=True):
     return dW, db, dfeat
 
 
+def ce_soft(score, label, class_weight=None, need_grad: bool = True):
+    """-> (out [1] f32 = soft / class-weighted CE, dscore [B, C] or None): ``aim_ce_soft`` (label [B, C] f32)."""
+    _chk(score, F32, "score"); _chk(label, F32, "label"); _chk(class_weight, F32, "class_weight")
+    B, C = score.shape
+    assert score.is_contiguous() and label.is_contiguous() and label.shape == score.shape
+    assert class_weight is None or (class_weight.is_contiguous() and class_weight.numel() == C)
+    dscore = torch.empty_like(score) if need_grad else None
+    ws = torch.empty((B, 2), dtype=F32, device=score.device)
+    out = torch.empty((1,), dtype=F32, device=score.device)
+    check(load_library().aim_ce_soft(score.data_ptr(), label.data_ptr(), _p(class_weight), _p(dscore), ws.data_ptr(),
+                                     out.data_ptr(), B, C, _stream()), "aim_ce_soft")
+    return out, dscore
+
+
 def ce_topk(score, label, k2: int = 5, need_grad: bool = True):
     """-> (out3 = [mean CE, top-1, top-k2] f32, dscore [B, C] = (softmax - onehot) / B or None)."""
     _chk(score, F32, "score")
@@ -564,6 +578,34 @@ def lambda_f32(scores, qkv, kx, lam, one_minus, BT, N, D, scale):
         _chk(t_, F32, n_)
     check(load_library().aim_lambda_f32(scores.data_ptr(), scores.stride(-2), qkv.data_ptr(), kx.data_ptr(), kx.stride(0),
                                         lam.data_ptr(), _p(one_minus), BT, N, D, scale, _stream()), "aim_lambda_f32")
+
+
+def _blend_args(imgs, B, blend):
+    if imgs.dtype not in (torch.float32, torch.uint8):
+        raise TypeError(f"patchify_blend: unsupported input dtype {imgs.dtype} (float32, uint8)")
+    if not imgs.is_cuda or not imgs.is_contiguous():
+        raise ValueError("patchify_blend: imgs must be a contiguous GPU tensor")
+    _chk(blend.partner, torch.int32, "partner")
+    if blend.partner.numel() != B or not blend.partner.is_contiguous():
+        raise ValueError(f"patchify_blend: partner must hold one index per clip ({B}), got {tuple(blend.partner.shape)}")
+    x1, y1, x2, y2 = blend.box
+    return (blend.partner.data_ptr(), blend.mode, blend.lam, blend.oml, x1, y1, x2, y2)
+
+
+def patchify_blend(imgs, A, B, T, H, W, p, Kp, mean3=None, std3=None, blend=None):
+    """``patchify`` with a mixup / cutmix of clip b and clip ``blend.partner[b]`` applied while gathering
+    (``blending.FusedBlend``; ``aim_patchify_blend``)."""
+    args = _blend_args(imgs, B, blend)
+    _chk(A, BF16, "A"); _chk(mean3, F32, "mean3"); _chk(std3, F32, "std3")
+    check(load_library().aim_patchify_blend(imgs.data_ptr(), _IN_DTYPES[imgs.dtype], _p(mean3), _p(std3), A.data_ptr(),
+                                            B, T, H, W, p, Kp, *args, _stream()), "aim_patchify_blend")
+
+
+def patchify_blend_f32(imgs, A, B, T, H, W, p, Kp, mean3=None, std3=None, blend=None):
+    args = _blend_args(imgs, B, blend)
+    _chk(A, F32, "A"); _chk(mean3, F32, "mean3"); _chk(std3, F32, "std3")
+    check(load_library().aim_patchify_blend_f32(imgs.data_ptr(), _IN_DTYPES[imgs.dtype], _p(mean3), _p(std3), A.data_ptr(),
+                                                B, T, H, W, p, Kp, *args, _stream()), "aim_patchify_blend_f32")
 
 
 def patchify_f32(imgs, A, B, T, H, W, p, Kp, mean3=None, std3=None):

@@ -2,21 +2,34 @@
 
 * ``Recognizer3D``  -- mmaction/models/recognizers/recognizer3d.py:8-118 + base.py:14-330
 * ``I3DHead``       -- mmaction/models/heads/i3d_head.py:9-73 + heads/base.py:27-108
-* ``CrossEntropyLoss`` -- mmaction/models/losses/cross_entropy_loss.py:9-80 (the hard-label branch, :78)
+* ``CrossEntropyLoss`` -- mmaction/models/losses/cross_entropy_loss.py:9-80 (hard and soft labels, ``class_weight``)
 * ``top_k_accuracy``   -- mmaction/core/evaluation/accuracy.py:90-109
 * ``GPUNormalize`` / ``register_module_hooks`` -- mmaction/utils/module_hooks.py:8-87 (fused into the
   patch-embedding kernel when the hooked module is this package's ``ViT_CLIP``).
+* ``train_cfg.blending`` -- ``LabelSmoothing`` / ``MixupBlending`` / ``CutmixBlending`` (blending.py) applied to every
+  training batch before ``forward_train`` (recognizers/base.py:104-107,254-255).  The ``vitclip_*_sthv2`` recipes use
+  ``LabelSmoothing(num_classes=174, smoothing=0.1)``.
 
 These are thin host modules; the hot path is the backbone.  On GPU tensors the K400 training tail runs on
-HIP kernels of libaim_hip.so: ``aim_head_fwd/bwd`` (avg-pool over frames + dropout + fc_cls)
-and ``aim_ce_topk`` (hard-label cross-entropy + top-1/top-5 in one launch, no ``.cpu().numpy()`` sync per iteration,
-heads/base.py:90).  ``_parse_losses`` reduces the log scalars in ONE all-reduce instead of four
+HIP kernels of libaim_hip.so: ``aim_head_fwd/bwd`` (avg-pool over frames + dropout + fc_cls),
+``aim_ce_topk`` (hard-label cross-entropy + top-1/top-5 in one launch, no ``.cpu().numpy()`` sync per iteration,
+heads/base.py:90) and ``aim_ce_soft`` (soft-label and class-weighted cross-entropy; hard labels with ``class_weight``
+go through it as an on-device one-hot).  ``_parse_losses`` reduces the log scalars in ONE all-reduce instead of four
 (recognizers/base.py:237-242) and hands them back as lazily materialised floats (no host sync until a logger reads
-them).  What the vit configs never use on this path -- soft labels, class weights, label smoothing, multi_class heads,
-non-average pooling, feature extraction, gradcam, backward hooks -- is NOT restated here: those keywords raise
-``NotImplementedError`` and belong to a real mmaction install (``register_into_mmaction``).  CPU tensors take a plain
-``F.cross_entropy`` / ``nn.Linear`` (host-logic tests only); if the HIP library is missing, a GPU call raises
-``LibraryNotBuilt`` -- it never falls back.
+them).
+
+Mixup and Cutmix on this package's backbones (float32 or uint8 clips on the GPU) are FUSED: the recognizer builds the
+soft labels, uploads the per-clip partner index and arms the backbone for its next forward, whose patch gather
+(``aim_patchify_blend``) blends the two clips as it reads them -- no blended copy of the clip batch is written.
+``Recognizer3D.fuse_blending = False`` forces the reference's materialised path.  One extension: with uint8 clips and a
+fused ``GPUNormalize`` hook, the fused Mixup blends the NORMALISED clips, ``lam * norm(a) + (1 - lam) * norm(b)``
+(the reference's Mixup turns uint8 into float and the hook's uint8 assert fires; the materialised path still does).
+
+What the vit configs never use on this path -- multi_class heads, ``I3DHead(label_smooth_eps=...)``, non-average
+pooling, feature extraction, gradcam, backward hooks -- is NOT restated here: those keywords raise
+``NotImplementedError`` and belong to a real mmaction install (``register_into_mmaction``).  CPU tensors take plain
+torch (host-logic tests only); if the HIP library is missing, a GPU call raises ``LibraryNotBuilt`` -- it never falls
+back.
 """
 from collections import OrderedDict
 
@@ -26,7 +39,8 @@ import torch.distributed as dist
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .registry import HEADS, LOSSES, RECOGNIZERS, Registry, build_backbone, build_head, build_loss
+from .registry import BLENDINGS, HEADS, LOSSES, RECOGNIZERS, Registry, build_backbone, build_head, build_loss
+from . import blending as _blending  # noqa: F401  (registers the BLENDINGS entries)
 
 MODULE_HOOKS = Registry("module_hooks")
 
@@ -140,23 +154,78 @@ class _CETopkFn(torch.autograd.Function):
         return dscore * g3[0], None
 
 
+class _CESoftFn(torch.autograd.Function):
+    """Soft-label / class-weighted cross-entropy from ``aim_ce_soft``; the gradient flows to the score only."""
+
+    @staticmethod
+    def forward(ctx, score, label, class_weight):
+        from . import ops
+        out, dscore = ops.ce_soft(score.detach().float().contiguous(), label.detach().float().contiguous(), class_weight,
+                                  need_grad=True)
+        ctx.save_for_backward(dscore)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        (dscore,) = ctx.saved_tensors
+        return dscore * g, None, None
+
+
+def _one_hot_rows(label, C):
+    """Hard labels -> one-hot rows on the device, a zero row where the label is outside [0, C) (what ignore_index = -100
+    does to F.cross_entropy's sum and denominator).  scatter_ only: no host sync."""
+    label = label.reshape(-1)
+    valid = (label >= 0) & (label < C)
+    out = torch.zeros((label.numel(), C), dtype=torch.float32, device=label.device)
+    return out.scatter_(1, label.clamp(0, C - 1).view(-1, 1), valid.to(torch.float32).view(-1, 1))
+
+
 @LOSSES.register_module()
 class CrossEntropyLoss(nn.Module):
-    """Hard-label cross entropy (cross_entropy_loss.py:78) times ``loss_weight`` (losses/base.py)."""
+    """Cross entropy (cross_entropy_loss.py:9-80) times ``loss_weight`` (losses/base.py).  Hard labels: ``F.cross_entropy``
+    (``weight=class_weight``); soft labels (``label`` shaped like ``cls_score``): ``mean_b(-sum_c y log_softmax)``, or with
+    ``class_weight`` ``sum_b sum_c w y (-log_softmax) / sum_b sum_c w y``.  GPU tensors run on ``aim_ce_topk`` (hard, no
+    weight) and ``aim_ce_soft`` (the rest)."""
 
     def __init__(self, loss_weight=1.0, class_weight=None):
         super().__init__()
-        if class_weight is not None:
-            raise NotImplementedError("CrossEntropyLoss(class_weight=...) is outside the AIM ViT-CLIP path")
         self.loss_weight = loss_weight
         self.class_weight = None
+        if class_weight is not None:
+            self.class_weight = torch.Tensor(class_weight)
+        self._cw_dev = None
+
+    def _weight_on(self, device):
+        if self.class_weight is None:
+            return None
+        if self._cw_dev is None or self._cw_dev.device != device:
+            self._cw_dev = self.class_weight.to(device=device, dtype=torch.float32).contiguous()
+        return self._cw_dev
 
     def forward(self, cls_score, label, **kwargs):
-        if kwargs or cls_score.size() == label.size():
-            raise NotImplementedError("soft labels / extra cross_entropy arguments are outside the AIM ViT-CLIP path")
+        if kwargs:
+            raise NotImplementedError("extra cross_entropy arguments are outside the AIM ViT-CLIP path")
+        if cls_score.size() == label.size():                     # soft labels (:52-76)
+            assert cls_score.dim() == 2, 'Only support 2-dim soft label'
+            if cls_score.is_cuda:
+                loss = _CESoftFn.apply(cls_score, label, self._weight_on(cls_score.device))     # aim_ce_soft
+            else:
+                lsm = F.log_softmax(cls_score, 1)
+                if self.class_weight is not None:
+                    lsm = lsm * self.class_weight.unsqueeze(0)
+                loss = -(label * lsm).sum(1)
+                if self.class_weight is not None:
+                    loss = loss.sum() / torch.sum(self.class_weight.unsqueeze(0) * label)
+                else:
+                    loss = loss.mean()
+            return loss * self.loss_weight
         if cls_score.is_cuda and cls_score.dim() == 2 and label.dtype == torch.int64:
-            return _CETopkFn.apply(cls_score, label)[0] * self.loss_weight      # aim_ce_topk
-        return F.cross_entropy(cls_score, label) * self.loss_weight
+            if self.class_weight is None:
+                return _CETopkFn.apply(cls_score, label)[0] * self.loss_weight      # aim_ce_topk
+            onehot = _one_hot_rows(label, cls_score.shape[1])                       # aim_ce_soft on a one-hot
+            return _CESoftFn.apply(cls_score, onehot, self._weight_on(cls_score.device)) * self.loss_weight
+        w = None if self.class_weight is None else self.class_weight.to(cls_score.device)
+        return F.cross_entropy(cls_score, label, weight=w) * self.loss_weight
 
 
 @HEADS.register_module()
@@ -197,13 +266,26 @@ class I3DHead(nn.Module):
         return self.fc_cls(pooled)
 
     def loss(self, cls_score, labels, **kwargs):
-        """heads/base.py:68-108 for hard labels: top-1 / top-5 accuracy + ``loss_cls``."""
+        """heads/base.py:68-108: hard labels give top-1 / top-5 accuracy + ``loss_cls``; soft labels (shaped like
+        ``cls_score``, e.g. from a ``train_cfg.blending``) give ``loss_cls`` only, as in the reference."""
         if kwargs:
             raise NotImplementedError("extra loss arguments are outside the AIM ViT-CLIP path")
         losses = dict()
         if labels.shape == torch.Size([]):
             labels = labels.unsqueeze(0)
+        elif labels.dim() == 1 and labels.size()[0] == self.num_classes and cls_score.size()[0] == 1:
+            labels = labels.unsqueeze(0)           # soft labels of a batch of one (heads/base.py:80-85)
+        if cls_score.size() == labels.size():
+            losses['loss_cls'] = self.loss_cls(cls_score, labels)
+            return losses
         if cls_score.is_cuda and cls_score.dim() == 2 and labels.dtype == torch.int64:
+            if self.loss_cls.class_weight is not None:       # weighted CE on aim_ce_soft, accuracy from aim_ce_topk
+                from . import ops
+                out3, _ = ops.ce_topk(cls_score.detach().float().contiguous(), labels.reshape(-1).contiguous(), 5,
+                                      need_grad=False)
+                losses['top1_acc'], losses['top5_acc'] = out3[1], out3[2]
+                losses['loss_cls'] = self.loss_cls(cls_score, labels)
+                return losses
             out3 = _CETopkFn.apply(cls_score, labels)        # CE + top-1/top-5 in one launch, nothing leaves the GPU
             losses['top1_acc'], losses['top5_acc'] = out3[1].detach(), out3[2].detach()
             losses['loss_cls'] = out3[0] * self.loss_cls.loss_weight
@@ -232,7 +314,13 @@ class Recognizer3D(nn.Module):
             assert isinstance(self.max_testing_views, int)
         if test_cfg and test_cfg.get('feature_extraction', False):
             raise NotImplementedError("test_cfg.feature_extraction is outside the AIM ViT-CLIP path")
+        # mini-batch blending, e.g. label smoothing, mixup, cutmix (recognizers/base.py:104-107)
         self.blending = None
+        if train_cfg is not None and 'blending' in train_cfg:
+            self.blending = BLENDINGS.build(train_cfg['blending'])
+        # Mixup / Cutmix fused into the backbone's patch gather where it can be (see the module docstring); False: always
+        # materialise the blended clips as the reference does
+        self.fuse_blending = True
         self.init_weights()
         self.fp16_enabled = False
 
@@ -316,12 +404,29 @@ class Recognizer3D(nn.Module):
             dist.all_reduce(packed.div_(dist.get_world_size()))
         return loss, LazyLogVars(list(log_vars.keys()), packed)
 
+    def _fusable(self, imgs):
+        from .backbone import ViT_CLIP
+        return (self.fuse_blending and self.blending.mode != 0 and imgs.is_cuda and imgs.dim() == 6
+                and imgs.dtype in (torch.float32, torch.uint8) and isinstance(self.backbone, ViT_CLIP))
+
+    def _blend(self, imgs, label):
+        """recognizers/base.py:254-255.  A fused Mixup / Cutmix leaves ``imgs`` untouched and arms the backbone's next
+        forward (like the fused GPUNormalize); everything else materialises through ``blending.apply``."""
+        bl = self.blending
+        plan = bl.draw(imgs.shape)
+        if self._fusable(imgs):
+            self.backbone._blend_next = bl.fused(plan, imgs.shape[1], imgs.device)
+            return imgs, bl.soft_label(label, plan)
+        return bl.apply(imgs, label, plan)
+
     def forward(self, imgs, label=None, return_loss=True, **kwargs):
         if kwargs.get('gradcam', False):
             raise NotImplementedError("gradcam is outside the AIM ViT-CLIP path")
         if return_loss:
             if label is None:
                 raise ValueError('Label should not be None.')
+            if self.blending is not None:
+                imgs, label = self._blend(imgs, label)
             return self.forward_train(imgs, label, **kwargs)
         return self.forward_test(imgs, **kwargs)
 

@@ -93,6 +93,8 @@ def build_from_cfg(cfg, registry: Registry, default_args: Optional[dict] = None)
 # one registry aliased four ways, like mmaction/models/builder.py:8-14
 MODELS = Registry("models")
 BACKBONES = HEADS = RECOGNIZERS = LOSSES = MODELS
+# mini-batch blendings of train_cfg.blending (mmaction/datasets/builder.py: a registry of its own)
+BLENDINGS = Registry("blending")
 
 
 def build_backbone(cfg):

@@ -32,7 +32,7 @@ extern "C" {
 
 typedef uint16_t aim_bf16;
 
-#define AIM_ABI_VERSION 6
+#define AIM_ABI_VERSION 7
 
 int aim_version(void);                /* == AIM_ABI_VERSION */
 const char* aim_last_error(void);     /* message of the last failing call on this thread */
@@ -255,6 +255,17 @@ int aim_qk_border(const aim_bf16* qkv, const aim_bf16* kx, int ldkx, float* ss, 
  * ------------------------------------------------------------------------------------------ */
 int aim_patchify(const void* imgs, int in_dtype /* 0 f32, 1 uint8, 2 bf16 */, const float* mean3, const float* std3, aim_bf16* A,
                  int B, int T, int H, int W, int p, int Kp, void* stream);
+/* patchify_blend: aim_patchify (in_dtype 0 f32 | 1 uint8) with a mini-batch blending applied while gathering, so no blended
+ * copy of the clip batch is written (mmaction/datasets/blending_utils.py:74-152 after recognizers/base.py:254-255).  Clip b
+ * pairs with clip partner[b] (int32 [B], device; b < B):
+ *   mode 1 (MixupBlending) : lam * v(b) + oml * v(partner[b]), each product and the sum rounded separately (oml = 1 - lam in
+ *                            f32, as torch computes it).  With mean3/std3 the clips are normalised first:
+ *                            lam * norm(a) + oml * norm(b) (the reference's own Mixup cannot take uint8 into GPUNormalize).
+ *   mode 2 (CutmixBlending): v(partner[b]) for pixels in rows [y1, y2) x columns [x1, x2) of every frame and channel, v(b)
+ *                            elsewhere (0 <= x1 <= x2 <= W, 0 <= y1 <= y2 <= H; lam / oml unused). */
+int aim_patchify_blend(const void* imgs, int in_dtype, const float* mean3, const float* std3, aim_bf16* A, int B, int T, int H,
+                       int W, int p, int Kp, const int32_t* partner, int mode, float lam, float oml, int x1, int y1, int x2,
+                       int y2, void* stream);
 int aim_embed_ln(const aim_bf16* tok, const float* cls, const float* pos, const float* temporal,
                  const float* gamma, const float* beta, float* x, float* mean, float* rstd,
                  int B, int T, int N, int D, float eps, void* stream);
@@ -326,6 +337,14 @@ int aim_head_bwd(const float* dscore, const float* pooled, const float* drop, co
                  float* dfeat, int B, int T, int D, int C, void* stream);
 int aim_ce_topk(const float* score, const int64_t* label, float* dscore, float* per_sample /* [B, 4] scratch */,
                 float* out3, int B, int C, int k2 /* second k of the accuracy pair, 5 */, void* stream);
+/* ce_soft : CrossEntropyLoss with soft labels and/or class_weight (mmaction/models/losses/cross_entropy_loss.py:52-80):
+ *           label [B, C] f32 (soft labels, or an on-device one-hot of hard labels with zero rows for ignored ones),
+ *           w = class_weight [C] or NULL (all ones).  loss_b = -sum_c w_c y_bc log_softmax(score)_bc;
+ *           out[0] = sum_b loss_b / denom with denom = B (w NULL: the plain mean) or sum_b sum_c w_c y_bc (weighted, as
+ *           F.cross_entropy(weight=w) and the reference's soft branch normalise); dscore[B, C] (or NULL) =
+ *           (softmax * sum_c w y - w y) / denom.  One workgroup per sample, then an ordered finish (bitwise reproducible). */
+int aim_ce_soft(const float* score, const float* label, const float* class_weight, float* dscore,
+                float* per_sample /* [B, 2] workspace */, float* out /* [1] */, int B, int C, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Reference-precision (fp32) path: `ViT_CLIP.set_precision('fp32')`, forward AND backward.  The product path
@@ -367,6 +386,9 @@ int aim_lambda_f32(const float* scores, int lds, const float* qkv, const float* 
                    float* one_minus_lam, int BT, int N, int D, float scale, void* stream);
 int aim_patchify_f32(const void* imgs, int in_dtype, const float* mean3, const float* std3, float* A, int B, int T,
                      int H, int W, int p, int Kp, void* stream);
+int aim_patchify_blend_f32(const void* imgs, int in_dtype, const float* mean3, const float* std3, float* A, int B, int T,
+                           int H, int W, int p, int Kp, const int32_t* partner, int mode, float lam, float oml, int x1, int y1,
+                           int x2, int y2, void* stream);    /* aim_patchify_blend with an f32 patch matrix */
 int aim_embed_ln_f32(const float* tok, const float* cls, const float* pos, const float* temporal, const float* gamma,
                      const float* beta, float* x, float* pre, float* mean, float* rstd, int B, int T, int N, int D, float eps,
                      void* stream);

@@ -1,0 +1,306 @@
+"""``train_cfg.blending`` on the GPU: the soft-label cross-entropy kernel (``aim_ce_soft``), the fused Mixup / Cutmix patch
+gathers (``aim_patchify_blend`` / ``aim_patchify_blend_f32``) against ``patchify`` of the materialised clips, and whole
+``Recognizer3D`` training steps with each blending, fused against ``fuse_blending = False`` (bf16 mode) and against the CPU
+oracle's fp32 autograd (fp32 mode)."""
+import copy
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import vit_clip_oracle as O
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+HERE = os.path.dirname(os.path.abspath(__file__))
+TOL = 1e-5          # tests/test_fp32_bwd_gpu.py: max |a - b| / max |b| per gradient tensor
+MEAN, STD = [123.675, 116.28, 103.53], [58.395, 57.12, 57.375]
+
+
+def _gen(seed):
+    return torch.Generator().manual_seed(seed)
+
+
+def _maxrel(a, b):
+    a, b = a.detach().double().cpu(), b.detach().double().cpu()
+    return ((a - b).abs().max() / b.abs().max()).item()
+
+
+# ---- aim_ce_soft -------------------------------------------------------------------------------------------------------
+def _soft_ce_ref(score, label, w):
+    """cross_entropy_loss.py:52-76 (and F.cross_entropy(weight=w) on one-hot rows) in float64 autograd."""
+    s = score.double().cpu().requires_grad_(True)
+    y = label.double().cpu()
+    lsm = torch.log_softmax(s, 1)
+    if w is not None:
+        lsm = lsm * w.double().cpu().unsqueeze(0)
+    loss = -(y * lsm).sum(1)
+    loss = loss.sum() / (w.double().cpu().unsqueeze(0) * y).sum() if w is not None else loss.mean()
+    loss.backward()
+    return loss.detach(), s.grad
+
+
+@pytest.mark.parametrize("B", [1, 3, 64])
+@pytest.mark.parametrize("C", [4, 174, 400, 1000])
+@pytest.mark.parametrize("weighted", [False, True])
+def test_ce_soft_against_autograd(B, C, weighted):
+    from aim_amd import ops
+    g = _gen(B * 1000 + C)
+    score = (torch.randn((B, C), generator=g) * 4).to(DEV)
+    label = torch.softmax(torch.randn((B, C), generator=g) * 3, 1)
+    if B > 1:
+        label[1] = 0.0                               # an ignored row (a one-hot of an out-of-range hard label)
+    label = label.to(DEV)
+    w = (torch.rand(C, generator=g) + 0.25).to(DEV) if weighted else None
+    out, dscore = ops.ce_soft(score, label, w)
+    ref_loss, ref_grad = _soft_ce_ref(score, label, w)
+    assert abs(out.item() - ref_loss.item()) <= 1e-5 * abs(ref_loss.item())
+    assert (dscore.double().cpu() - ref_grad).abs().max().item() <= 1e-6
+    out2, d2 = ops.ce_soft(score, label, w)
+    assert torch.equal(out, out2) and torch.equal(dscore, d2)           # ordered finish: bitwise on a repeat
+    out3, none = ops.ce_soft(score, label, w, need_grad=False)
+    assert none is None and torch.equal(out3, out)
+
+
+def test_cross_entropy_gpu_reproduces_reference_fixture():
+    """The reference's own CrossEntropyLoss values and autograd gradients (tests/golden/blending_ref.npz) through
+    aim_amd.CrossEntropyLoss on GPU tensors: aim_ce_soft for soft labels and for hard labels with class_weight."""
+    import aim_amd
+    z = np.load(os.path.join(HERE, "golden", "blending_ref.npz"))
+    names = sorted({k.split(".")[0] for k in z.files if k.startswith("loss_")})
+    assert len(names) >= 7
+    for name in names:
+        w = z[name + ".weight"]
+        fn = aim_amd.CrossEntropyLoss(class_weight=w.tolist() if w.size else None)
+        s = torch.from_numpy(z[name + ".score"]).to(DEV).requires_grad_(True)
+        loss = fn(s, torch.from_numpy(z[name + ".label"]).to(DEV))
+        loss.backward()
+        ref = float(z[name + ".loss"])
+        assert abs(loss.item() - ref) <= 1e-5 * abs(ref), name
+        assert (s.grad.cpu() - torch.from_numpy(z[name + ".grad"])).abs().max().item() <= 1e-6, name
+
+
+def test_weighted_hard_label_head_loss():
+    """Hard labels + class_weight: loss_cls equals F.cross_entropy(weight=w) (an ignored label included) and its gradient,
+    top-1 / top-5 still come from aim_ce_topk (an ignored label counts as a miss over all B samples)."""
+    import aim_amd
+    g = _gen(5)
+    w = torch.rand(9, generator=g) + 0.2
+    head = aim_amd.I3DHead(9, 16, loss_cls=dict(type='CrossEntropyLoss', class_weight=w.tolist()), dropout_ratio=0.0)
+    score = torch.randn((6, 9), generator=g).to(DEV).requires_grad_(True)
+    lab = torch.tensor([0, 8, -100, 3, 3, 1], device=DEV)
+    out = head.loss(score, lab)
+    out["loss_cls"].backward()
+    s = score.detach().cpu().double().requires_grad_(True)
+    ref = torch.nn.functional.cross_entropy(s, lab.cpu(), weight=w.double())
+    ref.backward()
+    assert abs(out["loss_cls"].item() - ref.item()) <= 1e-5 * ref.item()
+    assert (score.grad.double().cpu() - s.grad).abs().max().item() <= 1e-6
+    sc = score.detach().cpu()
+    ranks = [int((sc[i] > sc[i, l]).sum() + ((sc[i] == sc[i, l]) & (torch.arange(9) > l)).sum()) if l >= 0 else 99
+             for i, l in enumerate(lab.tolist())]
+    assert out["top1_acc"].item() == pytest.approx(sum(r < 1 for r in ranks) / 6)
+    assert out["top5_acc"].item() == pytest.approx(sum(r < 5 for r in ranks) / 6)
+
+
+# ---- fused patch gathers -----------------------------------------------------------------------------------------------
+def _plan(kind, B, lam, box, seed):
+    from aim_amd.blending import BlendPlan
+    perm = torch.randperm(B, generator=_gen(seed))
+    return BlendPlan(torch.tensor(lam, dtype=torch.float32), perm, box if kind == 2 else None)
+
+
+def _materialise(imgs6, kind, plan, norm):
+    """The clips the reference would feed the backbone, on the GPU with the reference's eager ops."""
+    from aim_amd.blending import CutmixBlending, MixupBlending
+    if kind == 2:
+        return CutmixBlending(10).mix_imgs(imgs6, plan)
+    if norm is None:
+        return MixupBlending(10).mix_imgs(imgs6, plan)
+    mean, std = (torch.tensor(v, device=DEV).view(1, 1, 3, 1, 1, 1) for v in norm)
+    x = (imgs6.float() - mean) / std                  # the uint8 extension: blend the normalised clips
+    return MixupBlending(10).mix_imgs(x, plan)
+
+
+CASES = [   # kind, p, H (= W), box (x1, y1, x2, y2)
+    (1, 16, 32, None), (1, 14, 28, None),
+    (2, 16, 48, (0, 0, 0, 0)), (2, 16, 48, (0, 0, 48, 48)), (2, 16, 48, (5, 9, 37, 30)), (2, 16, 48, (3, 3, 13, 47)),
+    (2, 16, 48, (16, 0, 32, 48)), (2, 14, 42, (7, 2, 35, 40)), (2, 14, 42, (0, 0, 42, 42)), (2, 14, 42, (20, 20, 20, 30)),
+]
+
+
+@pytest.mark.parametrize("dtype", ["f32", "u8"])
+@pytest.mark.parametrize("kind,p,H,box", CASES)
+def test_fused_patchify_bit_identical(kind, p, H, box, dtype):
+    from aim_amd import ops
+    from aim_amd.blending import CutmixBlending, MixupBlending
+    B, S, T = 3, 2, 2
+    g = _gen(kind * 100 + p + H)
+    if dtype == "f32":
+        imgs6 = (torch.randn((B, S, 3, T, H, H), generator=g) * 50).to(DEV)
+        norm = None
+    else:
+        imgs6 = torch.randint(0, 256, (B, S, 3, T, H, H), generator=g, dtype=torch.uint8).to(DEV)
+        norm = (MEAN, STD)
+    before = imgs6.clone()
+    plan = _plan(kind, B, 0.3731, box, 7)
+    bl = (MixupBlending if kind == 1 else CutmixBlending)(10)
+    fused = bl.fused(plan, S, DEV)
+    mat = _materialise(imgs6, kind, plan, norm).reshape(B * S, 3, T, H, H).contiguous()
+    imgs = imgs6.reshape(B * S, 3, T, H, H)
+    m3 = s3 = None
+    if norm is not None:
+        m3, s3 = torch.tensor(MEAN, device=DEV), torch.tensor(STD, device=DEV)
+    # the materialised clip goes through the unchanged gathers: uint8 Cutmix still normalises there, the normalised
+    # (float) Mixup does not
+    mm3, ms3 = (m3, s3) if mat.dtype == torch.uint8 else (None, None)
+    G2, K = (H // p) ** 2, 3 * p * p
+    Kp = (K + 63) // 64 * 64
+    rows = B * S * T * G2
+    a_ref, a_fused = torch.empty((rows, Kp), dtype=torch.bfloat16, device=DEV), torch.empty((rows, Kp), dtype=torch.bfloat16, device=DEV)
+    ops.patchify(mat, a_ref, B * S, T, H, H, p, Kp, mm3, ms3)
+    ops.patchify_blend(imgs, a_fused, B * S, T, H, H, p, Kp, m3, s3, blend=fused)
+    f_ref, f_fused = torch.empty((rows, K), device=DEV), torch.empty((rows, K), device=DEV)
+    ops.patchify_f32(mat, f_ref, B * S, T, H, H, p, K, mm3, ms3)
+    ops.patchify_blend_f32(imgs, f_fused, B * S, T, H, H, p, K, m3, s3, blend=fused)
+    torch.cuda.synchronize()
+    assert torch.equal(a_fused.view(torch.int16), a_ref.view(torch.int16))
+    assert torch.equal(f_fused.view(torch.int32), f_ref.view(torch.int32))
+    assert torch.equal(imgs6, before)
+    # every clip pairs with clip perm[b] * S + s
+    want = (plan.perm.view(-1, 1) * S + torch.arange(S)).reshape(-1).to(torch.int32)
+    assert torch.equal(fused.partner.cpu(), want)
+
+
+def test_fused_patchify_rejects_bad_arguments():
+    from aim_amd import ops
+    from aim_amd.blending import FusedBlend
+    imgs = torch.zeros((2, 3, 1, 32, 32), device=DEV)
+    A = torch.empty((8, 768), dtype=torch.bfloat16, device=DEV)
+    part = torch.tensor([1, 0], dtype=torch.int32, device=DEV)
+    with pytest.raises(RuntimeError, match="outside"):
+        ops.patchify_blend(imgs, A, 2, 1, 32, 32, 16, 768, blend=FusedBlend(part, 2, 1.0, 0.0, (0, 0, 33, 4)))
+    with pytest.raises(RuntimeError, match="mode"):
+        ops.patchify_blend(imgs, A, 2, 1, 32, 32, 16, 768, blend=FusedBlend(part, 3, 1.0, 0.0, (0, 0, 0, 0)))
+    with pytest.raises(ValueError, match="one index per clip"):
+        ops.patchify_blend(imgs, A, 2, 1, 32, 32, 16, 768, blend=FusedBlend(part[:1], 1, 0.5, 0.5, (0, 0, 0, 0)))
+
+
+# ---- whole training steps ----------------------------------------------------------------------------------------------
+BLENDS = {"smooth": dict(type='LabelSmoothing', num_classes=7, smoothing=0.1),
+          "mixup": dict(type='MixupBlending', num_classes=7, alpha=0.8, smoothing=0.1),
+          "cutmix": dict(type='CutmixBlending', num_classes=7, alpha=1.0)}
+
+
+def _recognizer(blend, seed=3, layers=2):
+    import aim_amd
+    cfg = dict(type='Recognizer3D',
+               backbone=dict(type='ViT_CLIP', input_resolution=32, num_frames=2, patch_size=16, width=128, layers=layers,
+                             heads=2, drop_path_rate=0.0, adapter_scale=0.5, pretrained=None),
+               cls_head=dict(type='I3DHead', in_channels=128, num_classes=7, spatial_type='avg', dropout_ratio=0.0),
+               train_cfg=dict(blending=dict(blend)), test_cfg=dict(average_clips='prob'))
+    torch.manual_seed(seed)
+    m = aim_amd.build_model(cfg)
+    for n, p in m.named_parameters():            # D_fc2 is zero-initialised: make every gradient path live
+        if "D_fc2" in n or "temporal_embedding" in n:
+            torch.nn.init.normal_(p, std=0.02)
+    torch.nn.init.normal_(m.cls_head.fc_cls.weight, std=0.1)
+    return m
+
+
+def _step(m, imgs, label, seed):
+    m.zero_grad(set_to_none=True)
+    torch.manual_seed(seed)
+    losses = m(imgs, label, return_loss=True)
+    loss, _ = m._parse_losses(losses)
+    loss.backward()
+    return losses, loss.detach(), {n: p.grad.detach().clone() for n, p in m.named_parameters() if p.requires_grad}
+
+
+def _uint8_hook(m):
+    import aim_amd
+    return aim_amd.register_module_hooks(m, [dict(type='GPUNormalize', input_format='NCTHW', mean=MEAN, std=STD)])
+
+
+@pytest.mark.parametrize("name", list(BLENDS))
+@pytest.mark.parametrize("dtype", ["f32", "u8"])
+def test_training_step_fused_equals_materialised_bf16(name, dtype):
+    """bf16 mode: the fused step and the reference's materialised one give the same loss and gradients, bit for bit."""
+    import aim_amd
+    m = _recognizer(BLENDS[name]).to(DEV)
+    assert isinstance(m.blending, aim_amd.BLENDINGS.get(BLENDS[name]["type"]))
+    g = _gen(11)
+    if dtype == "f32":
+        imgs = (torch.randn((4, 1, 3, 2, 32, 32), generator=g)).to(DEV)
+    else:
+        imgs = torch.randint(0, 256, (4, 1, 3, 2, 32, 32), generator=g, dtype=torch.uint8).to(DEV)
+        _uint8_hook(m)
+    label = torch.tensor([[1], [4], [6], [0]], device=DEV)
+    before = imgs.clone()
+    losses, loss_f, grads_f = _step(m, imgs, label, 21)
+    assert list(losses) == ["loss_cls"]                 # soft labels: no accuracy keys (heads/base.py:87-95)
+    assert torch.equal(imgs, before)
+    m.fuse_blending = False
+    if name == "mixup" and dtype == "u8":
+        # the reference's Mixup turns uint8 into float and GPUNormalize's uint8 assert fires; the materialised path keeps
+        # that behaviour, the fused one blends the normalised clips.  Compare with the float Mixup of normalised clips.
+        with pytest.raises(AssertionError, match="uint8"):
+            _step(m, imgs, label, 21)
+        from aim_amd.blending import MixupBlending
+        torch.manual_seed(21)
+        plan = m.blending.draw(imgs.shape)
+        assert isinstance(m.blending, MixupBlending)
+        for h in list(m.backbone._forward_pre_hooks):
+            del m.backbone._forward_pre_hooks[h]
+        mean, std = (torch.tensor(v, device=DEV).view(1, 1, 3, 1, 1, 1) for v in (MEAN, STD))
+        normed = (imgs.float() - mean) / std
+        mixed, soft = m.blending.apply(normed, label, plan)
+        m.blending, saved = None, m.blending
+        m.zero_grad(set_to_none=True)
+        losses_m = m(mixed, soft, return_loss=True)
+        loss_m, _ = m._parse_losses(losses_m)
+        loss_m.backward()
+        grads_m = {n: p.grad.detach().clone() for n, p in m.named_parameters() if p.requires_grad}
+        m.blending = saved
+        loss_m = loss_m.detach()
+    else:
+        _, loss_m, grads_m = _step(m, imgs, label, 21)
+    assert torch.equal(loss_f, loss_m), (loss_f.item(), loss_m.item())
+    assert sorted(grads_f) == sorted(grads_m)
+    bad = [n for n in grads_f if not torch.equal(grads_f[n], grads_m[n])]
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("name", list(BLENDS))
+def test_training_step_fp32_against_oracle(name):
+    """fp32 mode: loss and every trainable gradient of the fused step against an fp32 torch soft-CE over the CPU oracle's
+    backbone (autograd) on the materialised clips, at tests/test_fp32_bwd_gpu.py's bound."""
+    D, L, H, T, res, patch = 128, 2, 2, 2, 32, 16
+    m = _recognizer(BLENDS[name], layers=L)
+    st = O.synth_state_dict(O.backbone_param_shapes(res, T, patch, D, L), seed=31)
+    m.backbone.load_state_dict(st, strict=True)
+    head = {k: v.detach().clone() for k, v in m.cls_head.state_dict().items()}
+    m = m.to(DEV)
+    m.backbone.set_precision('fp32')
+    imgs = torch.randn((3, 1, 3, T, res, res), generator=_gen(12))
+    label = torch.tensor([[2], [5], [0]])
+    losses, loss, grads = _step(m, imgs.to(DEV), label.to(DEV), 41)
+    # the oracle: the same draws, the reference's materialised clips, autograd in fp32 on the CPU
+    bl = copy.deepcopy(m.blending)
+    torch.manual_seed(41)
+    mixed, soft = bl(imgs, label)
+    names = O.trainable_names(st)
+    ref_st = {k: v.clone().requires_grad_(k in names) for k, v in st.items()}
+    W, b = head["fc_cls.weight"].clone().requires_grad_(True), head["fc_cls.bias"].clone().requires_grad_(True)
+    feat = O.ref_backbone(mixed.reshape((-1,) + mixed.shape[2:]), ref_st, H, T, 0.5)
+    score = O.ref_i3d_head(feat, W, b)
+    ref_loss = -(soft * torch.log_softmax(score, 1)).sum(1).mean()
+    ref_loss.backward()
+    assert abs(loss.item() - ref_loss.item()) <= TOL * abs(ref_loss.item())
+    ref = {"backbone." + n: ref_st[n].grad for n in names}
+    ref["cls_head.fc_cls.weight"], ref["cls_head.fc_cls.bias"] = W.grad, b.grad
+    assert sorted(grads) == sorted(ref)
+    e = {n: _maxrel(grads[n], ref[n]) for n in ref}
+    worst = max(e, key=e.get)
+    assert e[worst] <= TOL, (worst, e[worst])
