@@ -521,7 +521,8 @@ def _block_forward(x, fz: _Frozen, adp: Dict[str, _AdapterW], B, T, N, H, dms1, 
         # N = 257 (ViT-L/14): the scores of tokens 0..255 against each other are ONE full tile per frame of the persistent
         # 256 x 256 kernel (8 slots); the 257th row and column and the cross scores come from one pass over q and k
         # (aim_qk_border: slots 8, 9).  Other N > 256 or N <= 128: the 128 x 128 kernel's tiles + qk_cross.
-        border = _EXPSUM_BORDER and N == 257 and D in (512, 1024) and _LAMBDA_ON_SIDE and _CLS_EARLY
+        border = (_EXPSUM_BORDER and N == 257 and D in (512, 1024) and _LAMBDA_ON_SIDE and _CLS_EARLY
+                  and ops.expsum_tiles(N - 1, N - 1) == 8)      # (slots 8, 9 sit behind the one tile's 8)
         nt = 10 if border else ops.expsum_tiles(N, N)
         part = _empty((BT, nt, 2), F32, dev)
         # the cross scores q_i . kx (one pass over q) go to the side stream as soon as q exists, beside the ow GEMM

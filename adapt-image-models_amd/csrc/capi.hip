@@ -43,6 +43,7 @@ extern "C" int aim_gemm_fp8(const aim_gemm_args* args, int epilogue, void* strea
     AIM_CHECK_ARG(g.M >= 1024 && g.N >= 64 && g.K > 0, "gemm_fp8: large-M problems only (M=%d N=%d K=%d)", g.M, g.N, g.K);
     AIM_CHECK_ARG((g.K % 16) == 0 && (g.lda % 16) == 0 && (g.ldw % 16) == 0, "gemm_fp8: K/lda/ldw must be multiples of 16 (K=%d lda=%d ldw=%d)", g.K, g.lda, g.ldw);
     AIM_CHECK_ARG((g.N % 8) == 0 && (g.n_split % 8) == 0 && (g.ldo % 8) == 0, "gemm_fp8: N, n_split and ldo must be multiples of 8");
+    AIM_CHECK_ARG(g.n_split >= 0 && g.n_split <= g.N, "gemm_fp8: n_split must be in [0, N] (n_split=%d N=%d)", g.n_split, g.N);
     AIM_CHECK_ARG((((g.K + 127) / 128) & 1) == 0, "gemm_fp8: ceil(K / 128) must be even (K=%d)", g.K);
     AIM_CHECK_ARG(g.A && g.W && g.out && !g.xrow, "gemm_fp8: null operand / unsupported xrow");
     if (epilogue == EPI_RES16)

@@ -148,7 +148,9 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs g) {
         if (lane == 0) red[4 + wave] = s;
         __syncthreads();
         if (tid == 0) {
-            float* po = (float*)g.out + ((long long)batch * gridDim.x + (tm * tiles_n + tn)) * 2;
+            // item `batch` owns gridDim.x pairs from float offset batch * ldo (ldo = 0: packed, 2 * gridDim.x)
+            const long long item = g.ldo > 0 ? g.ldo : 2LL * gridDim.x;
+            float* po = (float*)g.out + (long long)batch * item + (tm * tiles_n + tn) * 2;
             po[0] = mx;
             po[1] = red[4] + red[5] + red[6] + red[7];
         }
@@ -203,6 +205,9 @@ int aim_gemm_launch(const GemmArgs& g, int epi, int batch, hipStream_t st) {
     AIM_CHECK_ARG(g.A && g.W && g.out, "gemm: null operand");
     AIM_CHECK_ARG((long long)128 * g.lda * 2 < 0x7fffffffLL && (long long)128 * g.ldw * 2 < 0x7fffffffLL, "gemm: leading dimension too large");
     if (g.af || g.at || g.vec) AIM_CHECK_ARG(g.ntok > 0, "gemm: ntok required with row factors");
+    // the epilogues pick a column's activation and row factor once per group of 4 columns (gemm_epilogue.h: col_act / col_rs)
+    AIM_CHECK_ARG(g.n_split >= 0 && (g.n_split % 4) == 0 && g.n_split <= g.N,
+                  "gemm: n_split must be a multiple of 4 in [0, N] (n_split=%d N=%d)", g.n_split, g.N);
     // large-M problems run on the 256x256 pipelined kernel (gemm256.hip); AIM_GEMM_TILE=128 forces this file's.
     // Its epilogue moves 16 bytes per lane: bf16 outputs need N and the leading dimensions in multiples of 8.
     static const int pick = [] { const char* e = getenv("AIM_GEMM_TILE"); return e ? atoi(e) : 0; }();
@@ -239,6 +244,15 @@ int aim_gemm_launch(const GemmArgs& g, int epi, int batch, hipStream_t st) {
         AIM_CHECK_ARG(!g.xrow || (g.N < 256 && (g.ldx % 8) == 0), "gemm: EXPSUM extra key needs N < 256 and ldx %% 8 == 0");
         AIM_CHECK_ARG(g.ldo == 0 || g.ldo >= (g.xrow ? 32 : 16), "gemm: EXPSUM slot stride ldo=%d is smaller than the tile's own slots", g.ldo);
         return aim_gemm256_launch(g, epi, batch, st);
+    }
+    if (epi == EPI_EXPSUM) {
+        // this file's kernel writes one (max, sum) pair per 128 x 128 tile; aim_gemm_expsum_tiles reports 8 per item for every
+        // problem aim_expsum_use256 accepts, a layout only the 256 x 256 kernel writes (it needs K % 64 == 0)
+        const int tiles = ((g.M + 127) / 128) * ((g.N + 127) / 128);
+        AIM_CHECK_ARG(!aim_expsum_use256(g.M, g.N), "gemm: EXPSUM M=%d N=%d is laid out as 8 slots per item, which needs K %% 64 == 0 (K=%d)",
+                      g.M, g.N, g.K);
+        AIM_CHECK_ARG(g.ldo == 0 || g.ldo >= 2 * tiles, "gemm: EXPSUM slot stride ldo=%d is smaller than the item's own %d floats of slots", g.ldo,
+                      2 * tiles);
     }
     AIM_CHECK_ARG(!g.aux_frag, "gemm: aux_frag needs the large-tile kernel (ACT / DACT, batch 1, M >= 1024, N %% 8 == 0, K %% 64 == 0)");
     AIM_CHECK_ARG(!g.xrow, "gemm: `xrow` is only supported by the one-tile-per-item EXPSUM path");

@@ -112,7 +112,8 @@ def gemm(a: torch.Tensor, w: torch.Tensor, epi: int, out: torch.Tensor, *, bias=
     g.aux = _p(aux)
     g.ldaux = aux.stride(0) if aux is not None else 0
     g.out = out.data_ptr()
-    # EXPSUM: ldo = float stride between the (max, sum) slot groups of consecutive tiles (0: the tile's own 16 | 32)
+    # EXPSUM: ldo = float stride between the (max, sum) slot groups of consecutive batch items (0: packed, expsum_tiles pairs
+    # per item; 16 | 32 floats on the one-tile-per-item path)
     g.ldo = (out.stride(0) if out.dim() >= 2 else 0) if epi != EPI_EXPSUM else int(slot_stride)
     g.out2 = _p(out2)
     g.ldo2 = out2.stride(0) if out2 is not None else 0
@@ -149,7 +150,7 @@ def gemm(a: torch.Tensor, w: torch.Tensor, epi: int, out: torch.Tensor, *, bias=
 
 def gemm_fp8(a8: torch.Tensor, w8: torch.Tensor, wscale: torch.Tensor, epi: int, out: torch.Tensor, *, bias=None,
              resid=None, af=None, at=None, vec=None, bt=None, ntok: int = 0, act: int = 0, n_split: int = 0, act2: int = 0,
-             ldv: Optional[int] = None, reserve_cus: int = 0):
+             ldv: Optional[int] = None, reserve_cus: int = 0, probe=None):
     """``out = epilogue(wscale[n] * (a8 @ w8.T))``: fp8 e4m3 operands on the block-scaled MFMA (inference only).
     ``a8`` [M, K], ``w8`` [N, K] are float8_e4m3fn (or uint8 views); ``out`` bf16 (EPI_BF16), f32 (EPI_F32) or fp8
     (EPI_ACT8)."""
@@ -172,6 +173,8 @@ def gemm_fp8(a8: torch.Tensor, w8: torch.Tensor, wscale: torch.Tensor, epi: int,
     g.out, g.ldo = out.data_ptr(), out.stride(0)
     g.act, g.n_split, g.act2, g.scale = act, n_split, act2, 1.0
     g.reserve_cus = int(reserve_cus)
+    if probe is not None:                  # diagnostics: [cap, 4] int64 device tensor (as in gemm)
+        g.probe, g.probe_cap = probe.data_ptr(), probe.shape[0]
     if epi in (EPI_BF16, EPI_RES16):
         _chk(out, BF16, "out")
     elif epi == EPI_F32:

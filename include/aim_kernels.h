@@ -53,7 +53,10 @@ enum {
     AIM_EPI_F32 = 3,   /* out(f32) = resid + rs*(acc + bias) + bt[tok]*vec[frame][n]
                           (rs_bias_only != 0: out = resid + acc + rs*bias + ...)               */
     AIM_EPI_EXPSUM = 4,/* out(f32)[batch][tile][2] = (max, sum exp(scale*acc - max)) over the
-                          valid part of each 128x128 tile (lambda statistics, :149-151)         */
+                          valid part of each tile (lambda statistics, :149-151): per batch item
+                          aim_gemm_expsum_tiles(M, N) pairs, ldo = float stride between items
+                          (0: packed).  Problems that function lays out as 8 slots per item
+                          need K % 64 == 0; other K is refused.                                 */
     AIM_EPI_ACT8 = 5,  /* out(fp8 e4m3) = sat(rs * act(acc + bias)): inference only, nothing saved
                           for a backward (aim_gemm_fp8)                                         */
     AIM_EPI_RES16 = 6  /* out(bf16) = resid(bf16) + rs*(acc + bias) + bt[tok]*vec[frame][n]: AIM_EPI_F32's sum on
@@ -84,7 +87,8 @@ typedef struct aim_gemm_args {
     int32_t act;            /* AIM_ACT_*                                                        */
     int32_t rs_bias_only;   /* AIM_EPI_F32: apply rs to the bias term only                      */
     /* column split for fused [frozen MLP | adapter] GEMMs (ACT / DACT): when n_split > 0, columns
-       n < n_split use `act` with rs = 1, columns n >= n_split use `act2` with the row factor rs   */
+       n < n_split use `act` with rs = 1, columns n >= n_split use `act2` with the row factor rs.
+       n_split must be a multiple of 4 (8 for aim_gemm_fp8) and at most N; other values are refused. */
     int32_t n_split, act2;
     /* AIM_EPI_EXPSUM, one 256x256 tile per batch item (128 < max(M, N), N < 256) only: an EXTRA key.  Row N of W for batch
        item z is xrow + z * ldx (K elements); the scores against it (column N of the tile) are reduced apart into slots

@@ -143,10 +143,14 @@ def test_gemm_expsum_batched(N):
     BT, D = 3, 256
     qkv = rnd((BT * N, 3 * D), 21, 0.5, torch.bfloat16)
     nt = ops.expsum_tiles(N, N)
-    part = torch.zeros((BT, nt, 2), device=DEV)
+    # NaN-filled with a spare item behind: an unwritten slot or a write past the last item shows (a zero slot would
+    # contribute exp(0 + log 0) = 0 and hide)
+    buf = torch.full((BT + 1, nt, 2), float("nan"), device=DEV)
+    part = buf[:BT]
     q, k = qkv[:, :D], qkv[:, D:2 * D]
     ops.gemm(q, k, ops.EPI_EXPSUM, part, M=N, N=N, K=D, batch=BT, stride_a=N * 3 * D, stride_w=N * 3 * D,
              scale=0.125)
+    assert not torch.isnan(part).any() and torch.isnan(buf[BT]).all()
     s = torch.einsum("bik,bjk->bij", q.float().reshape(BT, N, D), k.float().reshape(BT, N, D)) * 0.125
     ref = torch.logsumexp(s.reshape(BT, -1), dim=1)
     got = torch.logsumexp(part[..., 0] + torch.log(part[..., 1]), dim=1)
@@ -388,10 +392,14 @@ def test_lambda():
     qkv = rnd((BT * N, 3 * D), 46, 0.35, torch.bfloat16)
     kx = rnd((BT, D), 47, 0.5, torch.bfloat16)
     nt = ops.expsum_tiles(N, N)
-    part = torch.zeros((BT, nt, 2), device=DEV)
+    # NaN-filled with a spare item behind: an unwritten slot or a write past the last item shows (a zero slot would
+    # contribute exp(0 + log 0) = 0 and hide)
+    buf = torch.full((BT + 1, nt, 2), float("nan"), device=DEV)
+    part = buf[:BT]
     q, k = qkv[:, :D], qkv[:, D:2 * D]
     ops.gemm(q, k, ops.EPI_EXPSUM, part, M=N, N=N, K=D, batch=BT, stride_a=N * 3 * D, stride_w=N * 3 * D,
              scale=0.125)
+    assert not torch.isnan(part).any() and torch.isnan(buf[BT]).all()
     lam, oml = torch.zeros(BT, device=DEV), torch.zeros(BT, device=DEV)
     ops.lambda_(qkv, kx, part, nt, lam, oml, BT, N, D, 0.125)
     # two-call form: the cross scores computed apart
@@ -633,6 +641,27 @@ def test_errors_are_loud():
         ops.gemm(a, w, ops.EPI_BF16, torch.zeros((8, 8), dtype=torch.bfloat16, device=DEV))
     with pytest.raises(RuntimeError, match="GPU tensor"):
         ops.gemm(a.cpu(), w, ops.EPI_BF16, torch.zeros((8, 8), dtype=torch.bfloat16, device=DEV))
+    # n_split is applied per group of 4 columns: anything else, or a split past N, is refused on every kernel
+    for M in (200, 600, 1100):
+        a, w = torch.zeros((M, 64), dtype=torch.bfloat16, device=DEV), torch.zeros((64, 64), dtype=torch.bfloat16, device=DEV)
+        post, pre = torch.zeros((M, 64), dtype=torch.bfloat16, device=DEV), torch.zeros((M, 64), dtype=torch.bfloat16, device=DEV)
+        for ns in (6, 68, -4):
+            with pytest.raises(RuntimeError, match="n_split"):
+                ops.gemm(a, w, ops.EPI_ACT, post, out2=pre, n_split=ns, act2=1)
+            with pytest.raises(RuntimeError, match="n_split"):
+                ops.gemm(a, w, ops.EPI_DACT, post, aux=pre, n_split=ns, act2=1)
+    # EXPSUM: a problem aim_gemm_expsum_tiles lays out as 8 slots per item needs K % 64 == 0; a slot stride smaller than
+    # the item's own slots is refused
+    qkv = torch.zeros((3 * 200, 3 * 72), dtype=torch.bfloat16, device=DEV)
+    assert ops.expsum_tiles(200, 200) == 8
+    with pytest.raises(RuntimeError, match="EXPSUM"):
+        ops.gemm(qkv, qkv[:, 72:], ops.EPI_EXPSUM, torch.zeros((3, 8, 2), device=DEV), M=200, N=200, K=72, batch=3,
+                 stride_a=200 * 216, stride_w=200 * 216, scale=0.125)
+    qkv = torch.zeros((3 * 300, 3 * 64), dtype=torch.bfloat16, device=DEV)
+    nt = ops.expsum_tiles(300, 300)
+    with pytest.raises(RuntimeError, match="slot stride"):
+        ops.gemm(qkv, qkv[:, 64:], ops.EPI_EXPSUM, torch.zeros((3, nt, 2), device=DEV), M=300, N=300, K=64, batch=3,
+                 stride_a=300 * 192, stride_w=300 * 192, scale=0.125, slot_stride=2 * nt - 2)
 
 
 # ---- classification tail: I3DHead + CrossEntropyLoss + top-k on HIP kernels ------------------------
