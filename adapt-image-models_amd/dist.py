@@ -86,7 +86,13 @@ class FlatAdamW:
     so that a step is one ``aim_adamw_flat`` launch per group and one all-reduce for the whole model.
 
     ``groups`` is a list of dicts like torch's param groups: ``{"params": [...], "lr":, "weight_decay":}``.
+
+    A step writes the parameters through raw pointers, so no tensor's ``_version`` changes.  Caches of converted weights learn
+    of it from ``FlatAdamW.generation`` (every step of every instance bumps it; ViT_ImageNet's bf16 operands) or from their
+    backbone's ``weights_epoch`` (attached backbones; the fp8 operands of ViT_CLIP).
     """
+
+    generation = 0          # class-wide count of steps taken by any FlatAdamW
 
     def __init__(self, groups, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
         from . import ops
@@ -276,6 +282,7 @@ class FlatAdamW:
                                      grad_scale=gs)
         for bb in self._backbones:                      # the update went through raw pointers: no tensor version changed
             bb.weights_epoch = getattr(bb, "weights_epoch", 0) + 1
+        FlatAdamW.generation += 1
 
     def state_dict(self):
         """torch.optim-shaped: ``state`` = per-parameter {step, exp_avg, exp_avg_sq} keyed by the parameter's index in

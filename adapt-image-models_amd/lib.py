@@ -97,9 +97,14 @@ SIGNATURES = {
     "aim_tattn_bwd_f32": [P, P, P, I, I, I, I, P],
     "aim_wgrad_f32_workspace_bytes": [I, I, I],
     "aim_wgrad_f32": [P, I, P, I, P, I, I, I, P, P, I, P, L, P],
+    "aim_embed_nopre_fwd": [P, P, P, P, P, I, I, I, I, P],
+    "aim_embed_nopre_bwd_workspace_bytes": [I, I, I, I],
+    "aim_embed_nopre_bwd": [P, I, P, P, P, P, P, I, I, I, I, P, L, P],
+    "aim_layernorm_gb_bwd_workspace_bytes": [I, I],
+    "aim_layernorm_gb_bwd": [P, I, L, P, L, P, P, P, P, I, I, P, L, P],
 }
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 
 def load_library():

@@ -407,6 +407,44 @@ def embed_bwd(dx, tok, cls, pos, temporal, gamma, mean, rstd, dtemporal, B, T, N
                             dtemporal.data_ptr(), B, T, N, D, ws.data_ptr(), nbytes, _stream()), "aim_embed_bwd")
 
 
+def embed_nopre_fwd(tok, cls, pos, temporal, x, B, T, N, D):
+    """ViT_ImageNet embedding (no ln_pre): x [B*T*N, D] = ((cls | tok) + pos) + temporal; tok f32 [B*T*(N-1), D] (conv + bias)."""
+    for n_, t_ in (("tok", tok), ("cls", cls), ("pos", pos), ("temporal", temporal), ("x", x)):
+        _chk(t_, F32, n_)
+    check(load_library().aim_embed_nopre_fwd(tok.data_ptr(), cls.data_ptr(), pos.data_ptr(), temporal.data_ptr(), x.data_ptr(),
+                                             B, T, N, D, _stream()), "aim_embed_nopre_fwd")
+
+
+def embed_nopre_bwd(dx, B, T, N, D, *, dtok=None, dcls=None, dpos=None, dtemporal=None, dbias=None):
+    """Backward of ``embed_nopre_fwd`` from dx [B*T*N, D] (bf16 or f32): ADDS into dcls [D], dpos [N, D], dtemporal [T, D] and
+    dbias [D] (fp32) and writes dtok [B*T*(N-1), D] (dx's dtype); any output may be None.  Fixed-order sums (reproducible)."""
+    _chk(dx, dx.dtype if dx.dtype in (F32, BF16) else F32, "dx")
+    _chk(dtok, dx.dtype, "dtok")
+    for n_, t_ in (("dcls", dcls), ("dpos", dpos), ("dtemporal", dtemporal), ("dbias", dbias)):
+        _chk(t_, F32, n_)
+    assert dx.is_contiguous() and (dtok is None or dtok.is_contiguous())
+    lib = load_library()
+    nbytes = lib.aim_embed_nopre_bwd_workspace_bytes(B, T, N, D)
+    ws = torch.empty((nbytes // 4,), dtype=F32, device=dx.device)
+    check(lib.aim_embed_nopre_bwd(dx.data_ptr(), int(dx.dtype == BF16), _p(dtok), _p(dcls), _p(dpos), _p(dtemporal), _p(dbias),
+                                  B, T, N, D, ws.data_ptr(), nbytes, _stream()), "aim_embed_nopre_bwd")
+
+
+def layernorm_gb_bwd(dy, x, mean, rstd, rows, D, dgamma, dbeta, *, lddy=None, ldx=None):
+    """LayerNorm affine gradients over ``rows`` rows: dgamma += sum dy * (x - mean) * rstd, dbeta += sum dy (fp32, ADDED).
+    Two-stage, fixed order: bitwise reproducible at any row count (aim_layernorm_bwd's own dgamma / dbeta use fp32 atomics
+    above 4 096 rows)."""
+    _chk(dy, dy.dtype if dy.dtype in (F32, BF16) else F32, "dy")
+    for n_, t_ in (("x", x), ("mean", mean), ("rstd", rstd), ("dgamma", dgamma), ("dbeta", dbeta)):
+        _chk(t_, F32, n_)
+    lib = load_library()
+    nbytes = lib.aim_layernorm_gb_bwd_workspace_bytes(rows, D)
+    ws = torch.empty((nbytes // 4,), dtype=F32, device=dy.device)
+    check(lib.aim_layernorm_gb_bwd(dy.data_ptr(), int(dy.dtype == BF16), dy.stride(0) if lddy is None else lddy, x.data_ptr(),
+                                   x.stride(0) if ldx is None else ldx, mean.data_ptr(), rstd.data_ptr(), _p(dgamma), _p(dbeta),
+                                   rows, D, ws.data_ptr(), nbytes, _stream()), "aim_layernorm_gb_bwd")
+
+
 def frame_sum(x, w, out, frames, ntok, D):
     _chk(x, x.dtype if x.dtype in (F32, BF16) else F32, "x"); _chk(w, F32, "w"); _chk(out, F32, "out")
     check(load_library().aim_frame_sum(x.data_ptr(), int(x.dtype == BF16), _p(w), out.data_ptr(), frames, ntok, D, _stream()),

@@ -32,7 +32,7 @@ extern "C" {
 
 typedef uint16_t aim_bf16;
 
-#define AIM_ABI_VERSION 7
+#define AIM_ABI_VERSION 8
 
 int aim_version(void);                /* == AIM_ABI_VERSION */
 const char* aim_last_error(void);     /* message of the last failing call on this thread */
@@ -408,6 +408,28 @@ int aim_tattn_bwd_f32(const float* qkv, const float* dout, float* dqkv, int B, i
 int64_t aim_wgrad_f32_workspace_bytes(int M, int Nw, int Kw);
 int aim_wgrad_f32(const float* G, int ldg, const float* A, int lda, float* dW, int M, int Nw, int Kw, float* db,
                   const float* at, int ntok, float* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * ViT_ImageNet (reference vit_imagenet.py; ABI 8): embedding without ln_pre and the LayerNorm gamma / beta gradients of the
+ * full-parameter backward.
+ *   embed_nopre_fwd : x[bt*N + n] = ((n == 0 ? cls : tok[bt*(N-1) + n-1]) + pos[n]) + temporal[t]   (tok f32 [B*T*(N-1), D]:
+ *                     the patch conv as a GEMM with its bias, :241-251; x f32 [B*T*N, D])
+ *   embed_nopre_bwd : from dx [B*T*N, D] (bf16 or f32): dcls += sum_bt dx[bt, 0]; dpos[n] += sum_bt dx[bt, n];
+ *                     dtemporal[t] += sum_{b, n} dx[b*T + t, n]; dbias += sum_{bt, n >= 1} dx[bt, n]; dtok (dx's dtype,
+ *                     [B*T*(N-1), D]) = the token rows of dx (the conv weight gradient's operand).  Every output is optional
+ *                     (NULL: skipped).  Fixed-order sums through the workspace: bitwise reproducible.
+ *   layernorm_gb_bwd: dgamma[d] += sum_m dy[m][d] * (x[m][d] - mean[m]) * rstd[m], dbeta[d] += sum_m dy[m][d] over any
+ *                     number of rows (row-chunk partial slabs, then an ordered sum: no atomics, bitwise reproducible).
+ * ------------------------------------------------------------------------------------------ */
+int aim_embed_nopre_fwd(const float* tok, const float* cls, const float* pos, const float* temporal, float* x, int B, int T,
+                        int N, int D, void* stream);
+int64_t aim_embed_nopre_bwd_workspace_bytes(int B, int T, int N, int D);
+int aim_embed_nopre_bwd(const void* dx, int dx_is_bf16, void* dtok, float* dcls, float* dpos, float* dtemporal, float* dbias,
+                        int B, int T, int N, int D, float* workspace, int64_t workspace_bytes, void* stream);
+int64_t aim_layernorm_gb_bwd_workspace_bytes(int rows, int D);
+int aim_layernorm_gb_bwd(const void* dy, int dy_is_bf16, int64_t lddy, const float* x, int64_t ldx, const float* mean,
+                         const float* rstd, float* dgamma, float* dbeta, int rows, int D, float* workspace,
+                         int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
