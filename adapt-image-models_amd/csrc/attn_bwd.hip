@@ -28,6 +28,12 @@ namespace {
 constexpr float LOG2E = 1.4426950408889634f;
 constexpr float C2 = 0.125f * LOG2E;      // 1/sqrt(dh) * log2(e): probabilities are recomputed in base 2
 
+// p = exp2(x) limited to [0, 1]: the limit is the clamp bit of the v_exp_f32 itself (no instruction of its own).  A true
+// probability never exceeds 1, but a key past N has a zero-filled K row, so s = 0 and x = -lse log2(e): for a query whose
+// log-sum-exp is below -88.7 (every logit strongly negative) exp2(x) is +inf, its dS is +-inf or NaN, and that times the zero
+// K^T row put NaN into dQ.  With p <= 1 the dS of such a key is finite and its zero K^T row removes it, as designed.
+__device__ __forceinline__ float prob_exp2(float x) { return __builtin_amdgcn_fmed3f(__builtin_amdgcn_exp2f(x), 0.f, 1.f); }
+
 __global__ __launch_bounds__(512, 4) void attn_bwd_dq_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ out,
                                                           const bf16_t* __restrict__ dout, const float* __restrict__ lse,
                                                           float* __restrict__ delta, bf16_t* __restrict__ dqkv, int N,
@@ -97,11 +103,11 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_dq_kernel(const bf16_t* __res
                     s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[ks], s, 0, 0, 0);
                     dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, dof[ks], dp, 0, 0, 0);
                 }
-                // No key mask: rows of K and V past N are zero-filled in LDS, so such a key has a finite p and its dS
-                // meets a zero K^T row in the dQ product.  The 1/sqrt(dh) factor of dS is applied once to dQ.
+                // No key mask: rows of K and V past N are zero-filled in LDS, so such a key has a finite p (prob_exp2: at
+                // most 1) and its dS meets a zero K^T row in the dQ product.  The 1/sqrt(dh) factor of dS is applied once to dQ.
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const float p = __builtin_amdgcn_exp2f(s[e] * C2 - L2);
+                    const float p = prob_exp2(s[e] * C2 - L2);
                     dsf[u * 4 + e] = (bf16_t)(p * dp[e]);
                 }
             }
@@ -720,7 +726,7 @@ __global__ __launch_bounds__(512) void attn_bwd_pipe_kernel(const bf16_t* __rest
                         bf16x4 ds4;
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
-                            const float p = __builtin_amdgcn_exp2f(s[e] * C2 - Lr[e]);
+                            const float p = prob_exp2(s[e] * C2 - Lr[e]);
                             pf[u][w * 4 + e] = (bf16_t)p;
                             const bf16_t d = (bf16_t)(p * dp[e]);
                             dsf[u][w * 4 + e] = d;
@@ -780,7 +786,7 @@ __global__ __launch_bounds__(512) void attn_bwd_pipe_kernel(const bf16_t* __rest
                     bf16x4 ds4;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        const float p = __builtin_amdgcn_exp2f(s[e] * C2 - Lr[e]);
+                        const float p = prob_exp2(s[e] * C2 - Lr[e]);
                         pf[u][e] = (bf16_t)p;
                         const bf16_t d = (bf16_t)(p * dp[e]);
                         dsf[u][e] = d;
