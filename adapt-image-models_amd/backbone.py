@@ -264,6 +264,10 @@ _AUX_FRAG = os.environ.get("AIM_AUX_FRAG", "1") != "0" and os.environ.get("AIM_G
 _DP_RESERVE = int(os.environ.get("AIM_DP_RESERVE_CUS", "0"))
 _FP8_RES16 = os.environ.get("AIM_FP8_RES16", "1") != "0"      # fp8 inference: bf16 residual stream (0: fp32, the A/B form)
 _EXPSUM_BORDER = os.environ.get("AIM_EXPSUM_BORDER", "1") != "0"      # N = 257: one 256 x 256 tile per frame + aim_qk_border
+# The head reads the class row of every frame and nothing else (ln_post, _BackboneFn.forward), so the LAST block computes its
+# spatial attention output, out_proj, ln_2 and the MLP + MLP_Adapter for those B*T rows only, and its backward starts from a
+# compact [B*T, D] gradient.  0 = the full-row last block (A/B runs and the equivalence test).
+_TOP_CLS_ONLY = os.environ.get("AIM_TOP_CLS_ONLY", "1") != "0"
 _QKV_RESERVE = int(os.environ.get("AIM_QKV_RESERVE", "32"))     # CUs the forward QKV GEMM leaves to the class-token chain (measured: 0/8/16 equal, 32 +0.7 %, 48 equal)
 
 
@@ -443,13 +447,20 @@ def _adapter_fwd_small(x_bf, ad: _AdapterW, rows, r, D, ar: _Arena, out_f32: boo
     return out, pre, h
 
 
-def _block_forward(x, fz: _Frozen, adp: Dict[str, _AdapterW], B, T, N, H, dms1, dms2, save: bool, f8: Optional[_Frozen8] = None):
+def _block_forward(x, fz: _Frozen, adp: Dict[str, _AdapterW], B, T, N, H, dms1, dms2, save: bool, f8: Optional[_Frozen8] = None,
+                   top: bool = False):
     """x: [B*T*N, D] f32 -> x2 (same shape).  Returns (x2, ctx) with ctx the tensors backward needs.
+
+    ``top`` (the last block, bf16 path): everything behind the QKV projection that only the class rows' result needs runs
+    on those B*T rows -- the spatial attention for the class query (``attn_fwd_cls``), out_proj, ln_2, the MLP and its
+    adapter (``ntok = 1``: a row is a frame, its token is 0) -- and x2 comes back as [B*T, D].  ln_1, the QKV projection, the
+    class-token chain and the lamda statistics need every token and are unchanged.
 
     ``f8`` (inference only, ``save`` must be False): the four large GEMMs of the block run on fp8 e4m3 operands
     (``aim_gemm_fp8``); their A operands are written as fp8 by the producing kernel (LayerNorm, attention, the FC
     epilogue).  The class-token chain (B*T rows) and the lamda statistics stay on the bf16 kernels."""
     assert f8 is None or not save
+    assert not (top and f8 is not None)
     dev = x.device
     M, D = x.shape
     BT = B * T
@@ -566,6 +577,10 @@ def _block_forward(x, fz: _Frozen, adp: Dict[str, _AdapterW], B, T, N, H, dms1, 
     if f8 is not None:
         ao, lse = _empty((M, D), ops.FP8, dev), None
         ops.attn_fwd_fp8(qkv, ao, BT, N, H)
+    elif top:          # the class query of every (frame, head): row 0 of attn_fwd's out and lse, bit for bit
+        ao = _empty((BT, D), BF16, dev)
+        lse = _empty((BT, H), F32, dev)
+        ops.attn_fwd_cls(qkv, ao, lse, BT, N, H)
     else:
         ao = _empty((M, D), BF16, dev)
         lse = _empty((BT, H, N), F32, dev)
@@ -596,18 +611,31 @@ def _block_forward(x, fz: _Frozen, adp: Dict[str, _AdapterW], B, T, N, H, dms1, 
         x2 = _empty((M, D), rdt, dev)
         ops.gemm_fp8(hcat, f8.Wcat2, f8.s2, epi_res, x2, bias=fz.bpr, resid=x1, vec=fz.b2row, ldv=0, bt=dms2, ntok=N)
         return x2, None
-    x1 = _empty((M, D), F32, dev)
-    ops.gemm(ao, fz.Wo, ops.EPI_F32, x1, bias=fz.bo, resid=x, af=oml, vec=sv, bt=dms1, ntok=N)
-    x2, xn, mean2, rstd2, hcat_pre, a_s = _mlp_adapter_forward(x1, fz, dms2, N, save)
+    if top:
+        # the class rows as the only token: resid = rows n == 0 of x (row stride N * D), factors of token 0.  small_tile: the
+        # 64 x 64 kernel sums K in the 256 x 256 kernel's order, so these rows get the bits the full-row launch gave them
+        x1 = _empty((BT, D), F32, dev)
+        ops.gemm(ao, fz.Wo, ops.EPI_F32, x1, bias=fz.bo, resid=x.view(BT, N * D)[:, :D], af=oml, vec=sv, bt=dms1[:1], ntok=1,
+                 small_tile=True)
+        x2, xn, mean2, rstd2, hcat_pre, a_s = _mlp_adapter_forward(x1, fz, dms2[:1], 1, save, small_tile=True)
+    else:
+        x1 = _empty((M, D), F32, dev)
+        ops.gemm(ao, fz.Wo, ops.EPI_F32, x1, bias=fz.bo, resid=x, af=oml, vec=sv, bt=dms1, ntok=N)
+        x2, xn, mean2, rstd2, hcat_pre, a_s = _mlp_adapter_forward(x1, fz, dms2, N, save)
     ctx = None
+    if save and top:
+        # ln_1's statistics of the class rows, packed for the backward's second, class-row launch
+        ctx = dict(top=True, mean1c=mean1.view(BT, N)[:, 0].contiguous(), rstd1c=rstd1.view(BT, N)[:, 0].contiguous())
+    elif save:
+        ctx = {}
     if save:
-        ctx = dict(x=x, mean1=mean1, rstd1=rstd1, qkv=qkv, probs=probs, ta=ta, t_pre=t_pre, t_h=t_h, lam=lam,
+        ctx.update(x=x, mean1=mean1, rstd1=rstd1, qkv=qkv, probs=probs, ta=ta, t_pre=t_pre, t_h=t_h, lam=lam,
                    oml=oml, ao=ao, lse=lse, sin=sin, s_pre=s_pre, s_h=s_h, x1=x1, mean2=mean2, rstd2=rstd2, xn=xn,
                    hcat_pre=hcat_pre, a_s=a_s, dms1=dms1, dms2=dms2)
     return x2, ctx
 
 
-def _mlp_adapter_forward(x1, fz: _Frozen, dms2, N, save: bool):
+def _mlp_adapter_forward(x1, fz: _Frozen, dms2, N, save: bool, small_tile: bool = False):
     """Joint adaptation (vit_clip.py:285-286; identical in vitclip_aim.py:209-210): x2 = x1 + mlp(ln_2(x1)) +
     drop_path(scale * MLP_Adapter(ln_2(x1))).  One GEMM for [c_fc | D_fc1] (N = 4D + r; QuickGELU on the MLP columns,
     dms2 * GELU on the adapter's) and one for [c_proj | D_fc2] (K = 4D + r); the adapter's token-scaled bias rides along
@@ -620,23 +648,25 @@ def _mlp_adapter_forward(x1, fz: _Frozen, dms2, N, save: bool):
     ops.layernorm_fwd(x1, fz.g2, fz.b2, M, D, D, y_bf16=xn, mean=mean2, rstd=rstd2)
     # the pre-activation is only needed by a backward: a no-grad forward passes no `out2` (the epilogue's stores to an empty
     # buffer resource are dropped: 658 MB per ViT-B block less to write)
-    frag = _AUX_FRAG and M >= 1024          # the large-tile kernel pair keeps it in its own fragment order (no re-tiling)
+    frag = _AUX_FRAG and M >= 1024 and not small_tile          # the large-tile kernel pair keeps it in its own fragment order (no re-tiling)
     if frag:
         hcat_pre = ops.frag_buffer(M, H4 + r, dev) if save else None
     else:
-        hcat_pre = _empty((M, H4 + r), BF16, dev) if (save or M < 1024) else None     # (the small-M kernel always stores it)
+        hcat_pre = _empty((M, H4 + r), BF16, dev) if (save or M < 1024 or small_tile) else None     # (the small-M kernels always store it)
     hcat = _empty((M, H4 + r), BF16, dev)
     ops.gemm(xn, fz.Wcat1, ops.EPI_ACT, hcat, bias=fz.bcat1, out2=hcat_pre, act=ops.ACT_QGELU, n_split=H4,
-             act2=ops.ACT_GELU, at=dms2, ntok=N, aux_grad=_AUX_GRAD, aux_frag=frag and hcat_pre is not None)
+             act2=ops.ACT_GELU, at=dms2, ntok=N, aux_grad=_AUX_GRAD, aux_frag=frag and hcat_pre is not None,
+             small_tile=small_tile)
     x2 = _empty((M, D), F32, dev)
-    ops.gemm(hcat, fz.Wcat2, ops.EPI_F32, x2, bias=fz.bpr, resid=x1, vec=fz.b2row, ldv=0, bt=dms2, ntok=N)
+    ops.gemm(hcat, fz.Wcat2, ops.EPI_F32, x2, bias=fz.bpr, resid=x1, vec=fz.b2row, ldv=0, bt=dms2, ntok=N, small_tile=small_tile)
     # the adapter's activation slice stays a VIEW of hcat (wgrad takes a row stride): no copy kernel in the forward, at the
     # price of keeping hcat (M x (4D + r) bf16) alive until this block's backward
     a_s = hcat[:, H4:] if save else None
     return x2, xn, mean2, rstd2, hcat_pre, a_s
 
 
-def _mlp_adapter_backward(dyb, x_in, mean2, rstd2, xn, hcat_pre, a_s, dms2, fz: _Frozen, gm, N, fsum=None):
+def _mlp_adapter_backward(dyb, x_in, mean2, rstd2, xn, hcat_pre, a_s, dms2, fz: _Frozen, gm, N, fsum=None,
+                          small_tile: bool = False):
     """Backward of ``_mlp_adapter_forward``: returns (d(x_in) as bf16, the weight-gradient closures).  x2 = x_in +
     [h | a_s] [W_proj | W2]^T + b_proj + dms2[tok] * b2.  ``fsum = (w [N], partial [frames, LN_FSUM_GROUPS, D])``: the ln_2
     backward also leaves the per-frame sums of w[n] * d(x_in) (in token groups) in ``partial``."""
@@ -651,13 +681,14 @@ def _mlp_adapter_backward(dyb, x_in, mean2, rstd2, xn, hcat_pre, a_s, dms2, fz: 
         ops.wgrad(dyb, a_s, gm["D_fc2.weight"], gm["D_fc2.bias"], at=dms2, ntok=N)
     dcat = _empty((M, H4 + r), BF16, dev)           # [dh_pre | da_pre]
     ops.gemm(dyb, fz.WcatT2, ops.EPI_DACT, dcat, aux=hcat_pre, act=ops.ACT_QGELU, n_split=H4, act2=ops.ACT_GELU,
-             at=dms2, ntok=N, aux_grad=_AUX_GRAD, aux_frag=_AUX_FRAG and dyb.shape[0] >= 1024, reserve_cus=_DP_RESERVE)
+             at=dms2, ntok=N, aux_grad=_AUX_GRAD, aux_frag=_AUX_FRAG and dyb.shape[0] >= 1024 and not small_tile,
+             reserve_cus=_DP_RESERVE, small_tile=small_tile)
     if _DETACH_BIG:
         big_later.append(lambda: ops.wgrad(dcat[:, H4:], xn, gm["D_fc1.weight"], gm["D_fc1.bias"]))
     else:
         ops.wgrad(dcat[:, H4:], xn, gm["D_fc1.weight"], gm["D_fc1.bias"])
     dxn = _empty((M, D), BF16, dev)
-    ops.gemm(dcat, fz.WcatT1, ops.EPI_BF16, dxn, reserve_cus=_DP_RESERVE)     # K = 4D + r: frozen c_fc dgrad + adapter D_fc1 dgrad
+    ops.gemm(dcat, fz.WcatT1, ops.EPI_BF16, dxn, reserve_cus=_DP_RESERVE, small_tile=small_tile)     # K = 4D + r: frozen c_fc dgrad + adapter D_fc1 dgrad
     dxb = _empty((M, D), BF16, dev)                  # (dcat stays alive in the D_fc1 weight-gradient closure)
     if fsum is not None:
         ops.layernorm_bwd_fsum(dxn, x_in, fz.g2, mean2, rstd2, dyb, dxb, fsum[0], fsum[1], M // N, N, D)
@@ -681,25 +712,39 @@ def _adapter_bwd_small(dout_bf, ad: _AdapterW, a_in, pre, h, grads, rows, r, D, 
 def _block_backward(dyb, c, fz: _Frozen, adp: Dict[str, _AdapterW], grads, B, T, N, H, keep: Optional[list] = None):
     """dyb = d(loss)/d(x2) [M, D] -> d(loss)/d(x); adapter grads accumulated into ``grads``.
 
+    A context of the top form (``_block_forward(top=True)``): dyb is the class rows' gradient [B*T, D]; the MLP / adapter
+    backward, the out_proj dgrad and the attention backward (``attn_bwd_cls``: one query per item, writes all of d(qkv)) run
+    on those rows, and ln_1's backward adds the residual gradient into the class rows with a second, B*T-row launch.
+
     The residual-stream GRADIENT is carried in bf16 (one tensor serves as the running residual gradient and
     as the dgrad GEMMs' operand; LayerNorm backward adds in fp32 and rounds once per block).  The forward
     residual stream stays fp32.  The reference's apex-O1 run keeps these gradients in fp16."""
     dev = dyb.device
-    M, D = dyb.shape
+    D = dyb.shape[1]
     BT = B * T
+    M = BT * N
     r, H4 = fz.r, 4 * D
+    top = bool(c.get("top"))
     # sum_n dms1[n] * d(x1)[frame, n, :] (the per-frame S_Adapter vector's gradient) comes out of the ln_2 backward itself
-    fpart = _empty((BT, ops.LN_FSUM_GROUPS, D), F32, dev) if _FSUM_IN_LN else None
-    dx1b, big_later = _mlp_adapter_backward(dyb, c["x1"], c["mean2"], c["rstd2"], c["xn"], c["hcat_pre"], c["a_s"], c["dms2"],
-                                            fz, grads["MLP_Adapter"], N, fsum=(c["dms1"], fpart) if _FSUM_IN_LN else None)
+    # (top form: the class row is the frame's only non-zero row of d(x1), so the sum is dms1[0] * that row)
+    fsum_in_ln = _FSUM_IN_LN and not top
+    fpart = _empty((BT, ops.LN_FSUM_GROUPS, D), F32, dev) if fsum_in_ln else None
+    if top:
+        dx1b, big_later = _mlp_adapter_backward(dyb, c["x1"], c["mean2"], c["rstd2"], c["xn"], c["hcat_pre"], c["a_s"],
+                                                c["dms2"][:1], fz, grads["MLP_Adapter"], 1, small_tile=True)
+    else:
+        dx1b, big_later = _mlp_adapter_backward(dyb, c["x1"], c["mean2"], c["rstd2"], c["xn"], c["hcat_pre"], c["a_s"], c["dms2"],
+                                                fz, grads["MLP_Adapter"], N, fsum=(c["dms1"], fpart) if fsum_in_ln else None)
     # ---- x1 = x + oml[f] * (ao Wo^T + bo) + dms1[tok] * s_vec[f]
     # class-token chain (S_Adapter, cross term, T_Adapter; a dozen kernels on B*T rows) on the side stream ...
     later: list = big_later       # the adapters' weight gradients: nobody downstream waits for them
     ar = _Arena(dev, 48 * BT * D + (1 << 16))      # side-stream tensors live in main-stream memory (see _Arena)
     with _Fork(dev, "bwd") as fork:
         dsv = ar.take((BT, D), F32)
-        if _FSUM_IN_LN:
+        if fsum_in_ln:
             ops.frame_sum(fpart, None, dsv, BT, ops.LN_FSUM_GROUPS, D)      # the groups' partial sums, in order
+        elif top:
+            ops.frame_sum(dx1b, c["dms1"][:1], dsv, BT, 1, D)
         else:
             ops.frame_sum(dx1b, c["dms1"], dsv, BT, N, D)
         # S_Adapter on the per-frame vector sin = lamda * crs ; crs = (xt Wv^T + bv) Wo^T + bo
@@ -732,11 +777,16 @@ def _block_backward(dyb, c, fz: _Frozen, adp: Dict[str, _AdapterW], grads, B, T,
     else:
         fork.run_detached(later, keep)
     # ... beside the spatial attention backward and the fused QKV dgrad on the main stream
-    dao = _empty((M, D), BF16, dev)
-    ops.gemm(dx1b, fz.WoT, ops.EPI_BF16, dao, af=c["oml"], ntok=N, reserve_cus=_DP_RESERVE)
     dqkv = _empty((M, 3 * D), BF16, dev)
-    delta = _empty((BT, H, N), F32, dev)
-    ops.attn_bwd(c["qkv"], c["ao"], dao, c["lse"], delta, dqkv, BT, N, H)
+    if top:
+        dao = _empty((BT, D), BF16, dev)
+        ops.gemm(dx1b, fz.WoT, ops.EPI_BF16, dao, af=c["oml"], ntok=1, small_tile=True)
+        ops.attn_bwd_cls(c["qkv"], c["ao"], dao, c["lse"], dqkv, BT, N, H)      # every row of dqkv: zeros in the other dQ rows
+    else:
+        dao = _empty((M, D), BF16, dev)
+        ops.gemm(dx1b, fz.WoT, ops.EPI_BF16, dao, af=c["oml"], ntok=N, reserve_cus=_DP_RESERVE)
+        delta = _empty((BT, H, N), F32, dev)
+        ops.attn_bwd(c["qkv"], c["ao"], dao, c["lse"], delta, dqkv, BT, N, H)
     del dao
     if not _LATE_JOIN:      # (A/B switch) join first and add the class rows into d(qkv) itself
         fork.join()
@@ -749,7 +799,14 @@ def _block_backward(dyb, c, fz: _Frozen, adp: Dict[str, _AdapterW], grads, B, T,
         ops.add_rows(dxl, N * D, dxl_cls)       # class rows: rows n == 0 of every frame
     # ---- ln_1
     dxb = _empty((M, D), BF16, dev)
-    ops.layernorm_bwd(dxl, c["x"], fz.g1, c["mean1"], c["rstd1"], M, D, lddy=D, ldx=D, lddx=D, dres=dx1b, dx_bf16=dxb)
+    if top:
+        # the residual gradient d(x1) is zero outside the class rows: all rows without it, then the class rows again from the
+        # same inputs with it (added in fp32, rounded once, as everywhere)
+        ops.layernorm_bwd(dxl, c["x"], fz.g1, c["mean1"], c["rstd1"], M, D, lddy=D, ldx=D, lddx=D, dx_bf16=dxb)
+        ops.layernorm_bwd(dxl, c["x"], fz.g1, c["mean1c"], c["rstd1c"], BT, D, lddy=N * D, ldx=N * D, lddx=N * D, dres=dx1b,
+                          lddres=D, dx_bf16=dxb)
+    else:
+        ops.layernorm_bwd(dxl, c["x"], fz.g1, c["mean1"], c["rstd1"], M, D, lddy=D, ldx=D, lddx=D, dres=dx1b, dx_bf16=dxb)
     return dxb
 
 
@@ -822,6 +879,8 @@ class _BackboneFn(torch.autograd.Function):
         # its context (~2 GB per ViT-B layer at 64 clips) just before that block's backward.  Bit-identical gradients
         # (same kernels, same inputs, same factors), ~1/3 more time, 1 / L of the activation memory.
         ckpt = bool(model.checkpoint) and need_grad
+        # the last block on the class rows only (a shape outside the attention kernels' range keeps the full-row form)
+        top = _TOP_CLS_ONLY and not aim and f8 is None and N <= 288
 
         def run_block(i, x_in, save):
             dms1, dms2 = masks[i, 0], masks[i, 1]
@@ -829,7 +888,7 @@ class _BackboneFn(torch.autograd.Function):
                 scale = float(model.transformer.resblocks[i].scale)
                 return aim_block_forward(x_in, frozen["blocks"][i], adp[i], B, T, N, H, dms1 * (1.0 / scale), dms2, save)
             return _block_forward(x_in, frozen["blocks"][i], adp[i], B, T, N, H, dms1, dms2, save,
-                                  f8=None if f8 is None else f8[i])
+                                  f8=None if f8 is None else f8[i], top=top and i == L - 1)
 
         if f8 is not None and _FP8_RES16:            # the fp8 path's residual stream is bf16
             x16 = _empty((M, D), BF16, dev)
@@ -846,11 +905,11 @@ class _BackboneFn(torch.autograd.Function):
         if x.dtype == BF16:
             ops.layernorm_fwd_x16(x, gw, gb, BT, D, N * D, y_f32=y)
         else:
-            ops.layernorm_fwd(x, gw, gb, BT, D, N * D, y_f32=y, mean=meanp, rstd=rstdp)
+            ops.layernorm_fwd(x, gw, gb, BT, D, D if top else N * D, y_f32=y, mean=meanp, rstd=rstdp)
         if need_grad:
             ctx.model, ctx.dims = model, (B, T, N, H, D, L)
             ctx.saved = dict(ctxs=ctxs, adp=adp, tok=tok, mean0=mean0, rstd0=rstd0, tmp=tmp, xL=x, gw=gw, meanp=meanp,
-                             rstdp=rstdp, params=params)
+                             rstdp=rstdp, params=params, top=top)
         return y.reshape(B, T, D).permute(0, 2, 1)      # '(b t) d -> b d t'
 
     @staticmethod
@@ -891,9 +950,14 @@ class _BackboneFn(torch.autograd.Function):
         dgw, dgb = buf(1), buf(2)
         dy = dout.permute(0, 2, 1).reshape(BT, D).contiguous().float()
         # ln_post backward touches the class rows only; every other row of the top gradient is zero
-        dxb = torch.zeros((M, D), dtype=BF16, device=dev)
-        ops.layernorm_bwd(dy, s["xL"], s["gw"], s["meanp"], s["rstdp"], BT, D, lddy=D, ldx=N * D, lddx=N * D,
-                          dx_bf16=dxb, dgamma=dgw, dbeta=dgb)
+        if s["top"]:        # the last block takes the class rows' gradient as it is: [B*T, D]
+            dxb = _empty((BT, D), BF16, dev)
+            ops.layernorm_bwd(dy, s["xL"], s["gw"], s["meanp"], s["rstdp"], BT, D, lddy=D, ldx=D, lddx=D,
+                              dx_bf16=dxb, dgamma=dgw, dbeta=dgb)
+        else:
+            dxb = torch.zeros((M, D), dtype=BF16, device=dev)
+            ops.layernorm_bwd(dy, s["xL"], s["gw"], s["meanp"], s["rstdp"], BT, D, lddy=D, ldx=N * D, lddx=N * D,
+                              dx_bf16=dxb, dgamma=dgw, dbeta=dgb)
         keep: list = []        # tensors the detached weight-gradient stream still reads; dropped after join_detached
         hook = model.grad_ready_hook
         blk_bwd = _block_backward

@@ -831,7 +831,168 @@ __global__ __launch_bounds__(512) void attn_bwd_pipe_kernel(const bf16_t* __rest
 #endif
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// Backward for ONE query per (frame, head): the last block, where the gradient of the attention output is non-zero in the
+// class row only (the head reads nothing else).  dO, O and the log-sum-exp come compact ([BT, D], [BT, H]); the whole
+// dqkv [BT N, 3 D] is written: dK, dV of every key, dQ in the class row and explicit zeros in every other dQ row (the QKV
+// dgrad reads all of it).  The q part of the other rows of qkv is never read.
+// The arithmetic of the class query is the full kernels', product for product: wave 0 runs the first query tile of the dq
+// kernel above with every query but the first zeroed (S^T = K Q^T, dP^T - delta = V dO^T from -delta, p = exp2(s C2 - L2),
+// dS = bf16(p (dP - delta)), dQ^T += K^T dS^T over 32 keys per MFMA in ascending order), delta = dO . O is summed as the
+// pipelined kernel sums it (8 lanes x 8 elements, DPP tree), and with a single non-zero query a key's dK = bf16(dS) q / 8 and
+// dV = bf16(p) dO are one exact product each -- what the matrix kernels' fp32 sums hold for it.  bf16(p) and bf16(dS) of
+// every key cross LDS once; then all eight waves write the rows: the kernel is bound by that traffic (K and V read once,
+// three times as much written).  One workgroup per item, no atomics, nothing summed across workgroups.
+__global__ __launch_bounds__(512, 4) void attn_bwd_cls_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ out,
+                                                              const bf16_t* __restrict__ dout, const float* __restrict__ lse,
+                                                              bf16_t* __restrict__ dqkv, int N, int H, int nkt) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    AIM_LDS char* sK = (AIM_LDS char*)smem_raw;
+    AIM_LDS char* sV = sK + nkt * 16 * 128;
+    AIM_LDS f32x2* sPD = (AIM_LDS f32x2*)(sV + nkt * 16 * 128);      // per key: bf16(p), bf16(dS) as floats
+
+    const int bid = (int)AIM_REV_BLOCK;          // (frame, head) items from the last one down: aim_common.h
+    const int bt = bid / H, h = bid - bt * H;
+    const int D = H * 64, ld = 3 * D;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int frow = lane & 15, fq = lane >> 4;
+    const bf16_t* base = qkv + (long long)bt * N * ld + h * 64;
+    const long long crow = (long long)bt * D + h * 64;               // the item's row of the compact dO / O
+    {
+        __amdgpu_buffer_rsrc_t rK = make_rsrc(base + D, ((long long)(N - 1) * ld + 64) * 2);
+        __amdgpu_buffer_rsrc_t rV = make_rsrc(base + 2 * D, ((long long)(N - 1) * ld + 64) * 2);
+        const int srow = lane >> 3, schunk = (lane & 7) ^ srow;
+        for (int p = wave; p < nkt * 2; p += 8) {
+            const int key = p * 8 + srow;
+            const unsigned voff = key < N ? (unsigned)((key * ld + schunk * 8) * 2) : AIM_OOB;
+            stage_piece(rK, sK + p * 1024, voff);
+            stage_piece(rV, sV + p * 1024, voff);
+        }
+    }
+    // every lane: its 16-byte chunk of q and dO (the write phase's factors) and delta, eight lanes to the row
+    const int sub = lane & 7;
+    float qw[8], dw[8];
+    float dl = 0.f;
+    {
+        const bf16x8 q8 = *(const bf16x8*)(base + sub * 8);
+        const bf16x8 d8 = *(const bf16x8*)(dout + crow + sub * 8);
+        const bf16x8 o8 = *(const bf16x8*)(out + crow + sub * 8);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            qw[e] = (float)q8[e];
+            dw[e] = (float)d8[e];
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) dl += (float)d8[e] * (float)o8[e];
+        dl += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, dl), 0xB1, 0xF, 0xF, true));
+        dl += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, dl), 0x4E, 0xF, 0xF, true));
+        dl += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, dl), 0x141, 0xF, 0xF, true));
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+
+    if (wave == 0) {
+        // the first query tile with the class query in column 0 and zeros in the other fifteen
+        bf16x8 qf[2], dof[2];
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            const int c = (ks * 4 + fq) * 8;
+            const bf16x8 z8 = {};
+            qf[ks] = z8;
+            dof[ks] = z8;
+            if (frow == 0) {
+                qf[ks] = *(const bf16x8*)(base + c);
+                dof[ks] = *(const bf16x8*)(dout + crow + c);
+            }
+        }
+        const float L2 = lse[(long long)bt * H + h] * LOG2E;
+        f32x4 dq[4];
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) dq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int kk = 0; kk < nkt / 2; ++kk) {
+            bf16x8 dsf;
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const int t = 2 * kk + u;
+                f32x4 s = f32x4{0.f, 0.f, 0.f, 0.f}, dp = f32x4{-dl, -dl, -dl, -dl};
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks) {
+                    const bf16x8 kf = lds_read8(sK + swz_off(t * 16 + frow, ks * 4 + fq));
+                    const bf16x8 vf = lds_read8(sV + swz_off(t * 16 + frow, ks * 4 + fq));
+                    s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[ks], s, 0, 0, 0);
+                    dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, dof[ks], dp, 0, 0, 0);
+                }
+                // keys past N: zero-filled K and V rows, a finite p (prob_exp2) and a zero K^T row in the dQ product
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float p = prob_exp2(s[e] * C2 - L2);
+                    const bf16_t pb = (bf16_t)p, db = (bf16_t)(p * dp[e]);
+                    dsf[u * 4 + e] = db;
+                    if (frow == 0) sPD[t * 16 + fq * 4 + e] = f32x2{(float)pb, (float)db};
+                }
+            }
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt) {
+                const int r0 = (2 * kk) * 16 + fq * 4 + (frow >> 2);
+                const int ch = dt * 2 + ((frow & 3) >> 1), half = (frow & 1) * 8;
+                const bf16x4 a = lds_read_tr4(sK + swz_off(r0, ch) + half);
+                const bf16x4 b = lds_read_tr4(sK + swz_off(r0 + 16, ch) + half);
+                bf16x8 ktf;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    ktf[e] = a[e];
+                    ktf[4 + e] = b[e];
+                }
+                dq[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ktf, dsf, dq[dt], 0, 0, 0);
+            }
+        }
+        bf16_t* op = dqkv + (long long)bt * N * ld + h * 64 + ((fq & 1) ? 16 + (fq - 1) * 4 : fq * 4);
+#pragma unroll
+        for (int dt = 0; dt < 4; dt += 2) {
+            const bf16x8 v = pair_rows16(
+                pack4(dq[dt][0] * 0.125f, dq[dt][1] * 0.125f, dq[dt][2] * 0.125f, dq[dt][3] * 0.125f),
+                pack4(dq[dt + 1][0] * 0.125f, dq[dt + 1][1] * 0.125f, dq[dt + 1][2] * 0.125f, dq[dt + 1][3] * 0.125f));
+            if (frow == 0) *(bf16x8*)(op + dt * 16) = v;
+        }
+    }
+    __syncthreads();
+    // every wave: the rows.  64 keys per trip, 8 lanes x 16 bytes per 64-wide row part
+    bf16_t* obase = dqkv + (long long)bt * N * ld + h * 64 + sub * 8;
+    const bf16x8 zero8 = {};
+    for (int j = tid >> 3; j < N; j += 64) {
+        const f32x2 pd = sPD[j];
+        bf16x8 dk8, dv8;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            dk8[e] = (bf16_t)(pd[1] * qw[e] * 0.125f);
+            dv8[e] = (bf16_t)(pd[0] * dw[e]);
+        }
+        bf16_t* orow = obase + (long long)j * ld;
+        if (j != 0) *(bf16x8*)orow = zero8;
+        *(bf16x8*)(orow + D) = dk8;
+        *(bf16x8*)(orow + 2 * D) = dv8;
+    }
+}
+
 }  // namespace
+
+extern "C" int aim_attn_bwd_cls(const aim_bf16* qkv, const aim_bf16* out_cls, const aim_bf16* dout_cls, const float* lse_cls,
+                                aim_bf16* dqkv, int BT, int N, int H, void* stream) {
+    AIM_CHECK_ARG(BT > 0 && N > 0 && H > 0 && N <= 288, "attn_bwd_cls: unsupported shape BT=%d N=%d H=%d (N <= 288)", BT, N, H);
+    AIM_CHECK_ARG(qkv && out_cls && dout_cls && lse_cls && dqkv, "attn_bwd_cls: null pointer");
+    const int nkt = ((N + 31) / 32) * 2;   // 16-key tiles, even
+    const int lds = nkt * 16 * 128 * 2 + nkt * 16 * 8;
+    static bool attr_set = false;
+    if (!attr_set) {
+        (void)hipFuncSetAttribute((const void*)attn_bwd_cls_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        attr_set = true;
+    }
+    hipLaunchKernelGGL(attn_bwd_cls_kernel, dim3(BT * H), dim3(512), lds, (hipStream_t)stream, (const bf16_t*)qkv,
+                       (const bf16_t*)out_cls, (const bf16_t*)dout_cls, lse_cls, (bf16_t*)dqkv, N, H, nkt);
+    AIM_CHECK_LAUNCH("aim_attn_bwd_cls");
+    return 0;
+}
 
 // workspace-free: delta is written into the caller-provided `delta` buffer ([BT, H, N] f32)
 extern "C" int aim_attn_bwd(const aim_bf16* qkv, const aim_bf16* out, const aim_bf16* dout, const float* lse,

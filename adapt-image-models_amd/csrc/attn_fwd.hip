@@ -28,7 +28,11 @@ namespace {
 // so only tiles >= NFULL carry masking code (N = 197: NKT = 14, NFULL = 12; masking every tile costs ~1.5x the
 // softmax's useful vector instructions in compares, selects and spilled condition masks).
 // OUT8: the output is written as fp8 e4m3 bytes (inference: operand of the fp8 out_proj GEMM) instead of bf16
-template <int NKT, int NFULL, bool OUT8 = false>
+// CLS: the class query (token 0) of every (frame, head) only -- the last block's form, whose other rows nobody reads.  K and V
+// are staged as always, the first 16-query tile runs and query row 0 is stored: out [BT, D], lse [BT, H].  The arithmetic
+// of that row is the full kernel's (a query is one MFMA column and one lane quartet: the tile's other queries do not
+// touch it, whatever they hold).
+template <int NKT, int NFULL, bool OUT8 = false, bool CLS = false>
 __global__ __launch_bounds__(512, 4) void attn_fwd_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
                                                           float* __restrict__ lse, int N, int H
 #ifdef AIM_X_STAMPS
@@ -55,7 +59,7 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_kernel(const bf16_t* __restri
     const float C2 = 0.125f * 1.4426950408889634f;   // 1/sqrt(dh) * log2(e): softmax runs in base 2
 
     const bf16_t* base = qkv + (long long)bt * N * ld + h * 64;
-    const int nqt = (N + 15) >> 4;
+    const int nqt = CLS ? 1 : (N + 15) >> 4;
     // first query tile's fragments are requested before the K/V staging so their latency overlaps it
     bf16x8 qf[2];
     {
@@ -135,7 +139,11 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_kernel(const bf16_t* __restri
             }
         sum = quad_sum(sum);
         const float inv = 1.0f / sum;
-        if (fq == 0 && q < N && lse) lse[((long long)bt * H + h) * N + q] = mx * 0.125f + __logf(sum);
+        if constexpr (CLS) {
+            if (lane == 0 && lse) lse[(long long)bt * H + h] = mx * 0.125f + __logf(sum);
+        } else {
+            if (fq == 0 && q < N && lse) lse[((long long)bt * H + h) * N + q] = mx * 0.125f + __logf(sum);
+        }
 
         ATT_STAMPQ(2);
         f32x4 o[4];
@@ -176,12 +184,13 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_kernel(const bf16_t* __restri
         } else {
             // 16-byte stores: tiles (dt, dt+1) are paired across the even / odd 16-lane rows (aim_common.h pair_rows16), so a
             // lane writes 8 consecutive head-dim elements and a row's four lanes cover 64 contiguous bytes
-            bf16_t* op = out + ((long long)bt * N + (q < N ? q : 0)) * D + h * 64 + ((fq & 1) ? 16 + (fq - 1) * 4 : fq * 4);
+            const long long orow = CLS ? (long long)bt : (long long)bt * N + (q < N ? q : 0);
+            bf16_t* op = out + orow * D + h * 64 + ((fq & 1) ? 16 + (fq - 1) * 4 : fq * 4);
 #pragma unroll
             for (int dt = 0; dt < 4; dt += 2) {
                 const bf16x8 v = pair_rows16(pack4(o[dt][0] * inv, o[dt][1] * inv, o[dt][2] * inv, o[dt][3] * inv),
                                              pack4(o[dt + 1][0] * inv, o[dt + 1][1] * inv, o[dt + 1][2] * inv, o[dt + 1][3] * inv));
-                if (q < N) *(bf16x8*)(op + dt * 16) = v;
+                if (CLS ? q == 0 : q < N) *(bf16x8*)(op + dt * 16) = v;
             }
         }
         ATT_STAMPQ(4);
@@ -195,23 +204,23 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_kernel(const bf16_t* __restri
 #endif
 }
 
-template <int NKT, int NFULL, bool OUT8 = false>
+template <int NKT, int NFULL, bool OUT8 = false, bool CLS = false>
 int launch_nf(const aim_bf16* qkv, aim_bf16* out, float* lse, int BT, int N, int H, hipStream_t st) {
-    hipLaunchKernelGGL((attn_fwd_kernel<NKT, NFULL, OUT8>), dim3(BT * H), dim3(512), NKT * 16 * 128 * 2, st, (const bf16_t*)qkv,
+    hipLaunchKernelGGL((attn_fwd_kernel<NKT, NFULL, OUT8, CLS>), dim3(BT * H), dim3(512), NKT * 16 * 128 * 2, st, (const bf16_t*)qkv,
                        (bf16_t*)out, lse, N, H
 #ifdef AIM_X_STAMPS
                        , g_attn_probe
 #endif
     );
-    AIM_CHECK_LAUNCH("aim_attn_fwd");
+    AIM_CHECK_LAUNCH(CLS ? "aim_attn_fwd_cls" : "aim_attn_fwd");
     return 0;
 }
 
 // masking code only on the last two key tiles when N reaches into them, on every tile otherwise
-template <int NKT, bool OUT8 = false>
+template <int NKT, bool OUT8 = false, bool CLS = false>
 int launch(const aim_bf16* qkv, aim_bf16* out, float* lse, int BT, int N, int H, hipStream_t st) {
-    if ((N >> 4) >= NKT - 2) return launch_nf<NKT, NKT - 2, OUT8>(qkv, out, lse, BT, N, H, st);
-    return launch_nf<NKT, 0, OUT8>(qkv, out, lse, BT, N, H, st);
+    if ((N >> 4) >= NKT - 2) return launch_nf<NKT, NKT - 2, OUT8, CLS>(qkv, out, lse, BT, N, H, st);
+    return launch_nf<NKT, 0, OUT8, CLS>(qkv, out, lse, BT, N, H, st);
 }
 
 }  // namespace
@@ -224,6 +233,16 @@ extern "C" int aim_attn_fwd(const aim_bf16* qkv, aim_bf16* out, float* lse, int 
     if (N <= 64) return launch<4>(qkv, out, lse, BT, N, H, st);
     if (N <= 224) return launch<14>(qkv, out, lse, BT, N, H, st);
     return launch<18>(qkv, out, lse, BT, N, H, st);
+}
+
+extern "C" int aim_attn_fwd_cls(const aim_bf16* qkv, aim_bf16* out_cls, float* lse_cls, int BT, int N, int H, void* stream) {
+    AIM_CHECK_ARG(BT > 0 && N > 0 && H > 0 && N <= 288, "attn_fwd_cls: unsupported shape BT=%d N=%d H=%d (N <= 288)", BT, N, H);
+    AIM_CHECK_ARG(qkv && out_cls && lse_cls, "attn_fwd_cls: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    if (N <= 32) return launch<2, false, true>(qkv, out_cls, lse_cls, BT, N, H, st);
+    if (N <= 64) return launch<4, false, true>(qkv, out_cls, lse_cls, BT, N, H, st);
+    if (N <= 224) return launch<14, false, true>(qkv, out_cls, lse_cls, BT, N, H, st);
+    return launch<18, false, true>(qkv, out_cls, lse_cls, BT, N, H, st);
 }
 
 extern "C" int aim_attn_fwd_fp8(const aim_bf16* qkv, uint8_t* out_fp8, float* lse, int BT, int N, int H, void* stream) {

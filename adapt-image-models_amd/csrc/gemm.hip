@@ -262,7 +262,7 @@ int aim_gemm_launch(const GemmArgs& g, int epi, int batch, hipStream_t st) {
     // the critical path and the kernel is neutral (1 274 vs 1 277 clips/s), so this file's 128 x 128 kernel keeps those.
     // AIM_GEMM_SMALL=rows moves the threshold (0: never).
     static const int small_rows = [] { const char* e = getenv("AIM_GEMM_SMALL"); return e ? atoi(e) : 256; }();
-    if ((g.M <= small_rows || g.row0 != 0) && epi != EPI_EXPSUM && (g.K % 64) == 0) {
+    if ((g.M <= small_rows || g.row0 != 0 || g.small_tile) && epi != EPI_EXPSUM && (g.K % 64) == 0) {
         if (epi == EPI_ACT) AIM_CHECK_ARG(g.out2 && (g.ldo2 % 4) == 0, "gemm: ACT epilogue needs out2");
         if (epi == EPI_DACT) AIM_CHECK_ARG(g.aux && (g.ldaux % 4) == 0, "gemm: DACT epilogue needs aux");
         return aim_gemm_small_launch(g, epi, batch, st);

@@ -84,8 +84,8 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const TDY* __restrict__ dy,
                                                      const float* __restrict__ x, long long ldx,
                                                      const float* __restrict__ gamma, const float* __restrict__ mean,
                                                      const float* __restrict__ rstd, const TDR* __restrict__ dres,
-                                                     float* __restrict__ dx, bf16_t* __restrict__ dxb, long long lddx,
-                                                     float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                                     long long lddres, float* __restrict__ dx, bf16_t* __restrict__ dxb,
+                                                     long long lddx, float* __restrict__ dgamma, float* __restrict__ dbeta,
                                                      int rows, int D) {
     const int lane = threadIdx.x & 63;
     const int row = (int)AIM_REV_BLOCK * 4 + (threadIdx.x >> 6);
@@ -133,9 +133,9 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const TDY* __restrict__ dy,
             for (int e = 0; e < 4; ++e) o[e] = rs * (g[c][e] - m1 - xh[c][e] * m2);
             if (dres) {
                 if constexpr (sizeof(TDR) == 4) {
-                    o += *(const f32x4*)(dres + (long long)row * lddx + ch * 4);
+                    o += *(const f32x4*)(dres + (long long)row * lddres + ch * 4);
                 } else {
-                    const bf16x4 rb = *(const bf16x4*)(dres + (long long)row * lddx + ch * 4);
+                    const bf16x4 rb = *(const bf16x4*)(dres + (long long)row * lddres + ch * 4);
                     o += f32x4{(float)rb[0], (float)rb[1], (float)rb[2], (float)rb[3]};
                 }
             }
@@ -326,13 +326,14 @@ constexpr int AIM_LN_DPARAM_ROWS = 8192;
 }  // namespace
 
 extern "C" int aim_layernorm_bwd(const void* dy, int dy_is_bf16, int64_t lddy, const float* x, int64_t ldx, const float* gamma,
-                                 const float* mean, const float* rstd, const void* dres, int dres_is_bf16, float* dx,
-                                 aim_bf16* dx_bf16, int64_t lddx, float* dgamma, float* dbeta, int rows, int D,
+                                 const float* mean, const float* rstd, const void* dres, int dres_is_bf16, int64_t lddres,
+                                 float* dx, aim_bf16* dx_bf16, int64_t lddx, float* dgamma, float* dbeta, int rows, int D,
                                  void* stream) {
     AIM_CHECK_ARG(rows > 0 && D > 0 && (D % 4) == 0 && D <= MAXC * 256, "layernorm_bwd: bad shape rows=%d D=%d", rows, D);
     AIM_CHECK_ARG(dy && x && gamma && mean && rstd && (dx || dx_bf16), "layernorm_bwd: null pointer");
     AIM_CHECK_ARG((!dgamma) == (!dbeta), "layernorm_bwd: dgamma and dbeta go together");
-    AIM_CHECK_ARG((ldx % 4) == 0 && (lddy % 4) == 0 && (lddx % 4) == 0, "layernorm_bwd: strides must be multiples of 4");
+    AIM_CHECK_ARG((ldx % 4) == 0 && (lddy % 4) == 0 && (lddx % 4) == 0 && (!dres || (lddres % 4) == 0),
+                  "layernorm_bwd: strides must be multiples of 4");
     if (dgamma && rows <= AIM_LN_DPARAM_ROWS) {      // parameter gradients apart, in a fixed order
         if (dy_is_bf16)
             hipLaunchKernelGGL(ln_dparam_kernel<bf16_t>, dim3((D + 63) / 64), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy,
@@ -346,8 +347,8 @@ extern "C" int aim_layernorm_bwd(const void* dy, int dy_is_bf16, int64_t lddy, c
     }
 #define AIM_LN_BWD_T(NC, TDY, TDR)                                                                                  \
     hipLaunchKernelGGL((ln_bwd_kernel<NC, TDY, TDR>), dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream,        \
-                       (const TDY*)dy, (long long)lddy, x, (long long)ldx, gamma, mean, rstd, (const TDR*)dres, dx,   \
-                       (bf16_t*)dx_bf16, (long long)lddx, dgamma, dbeta, rows, D)
+                       (const TDY*)dy, (long long)lddy, x, (long long)ldx, gamma, mean, rstd, (const TDR*)dres,       \
+                       (long long)lddres, dx, (bf16_t*)dx_bf16, (long long)lddx, dgamma, dbeta, rows, D)
 #define AIM_LN_BWD(NC)                                                                                              \
     if (dy_is_bf16 && dres_is_bf16) AIM_LN_BWD_T(NC, bf16_t, bf16_t);                                               \
     else if (dy_is_bf16) AIM_LN_BWD_T(NC, bf16_t, float);                                                           \

@@ -31,6 +31,7 @@ class GemmArgs(Structure):
         ("xrow", c_void_p), ("ldx", c_int32),
         ("reserve_cus", c_int32), ("probe", c_void_p), ("probe_cap", c_int32),
         ("wscale", c_void_p), ("aux_grad", c_int32), ("aux_frag", c_int32), ("row0", c_int32),
+        ("small_tile", c_int32),
     ]
 
 
@@ -52,11 +53,13 @@ SIGNATURES = {
     "aim_layernorm_fwd": [P, L, P, P, P, P, L, P, P, I, I, F, P],
     "aim_layernorm_fwd_fp8": [P, L, P, P, P, L, I, I, F, P],
     "aim_layernorm_fwd_x16": [P, L, P, P, P, P, P, L, I, I, F, P],
-    "aim_layernorm_bwd": [P, I, L, P, L, P, P, P, P, I, P, P, L, P, P, I, I, P],
+    "aim_layernorm_bwd": [P, I, L, P, L, P, P, P, P, I, L, P, P, L, P, P, I, I, P],
     "aim_layernorm_bwd_fsum": [P, L, P, L, P, P, P, P, P, L, P, P, I, I, I, I, P],
     "aim_attn_fwd": [P, P, P, I, I, I, P],
     "aim_attn_fwd_fp8": [P, P, P, I, I, I, P],
     "aim_attn_bwd": [P, P, P, P, P, P, I, I, I, P],
+    "aim_attn_fwd_cls": [P, P, P, I, I, I, P],
+    "aim_attn_bwd_cls": [P, P, P, P, P, I, I, I, P],
     "aim_cls_attn_fwd": [P, P, P, I, I, I, I, P],
     "aim_cls_attn_bwd": [P, P, P, P, I, I, I, I, I, P],
     "aim_tattn_fwd": [P, P, P, I, I, I, I, P],
@@ -104,7 +107,7 @@ SIGNATURES = {
     "aim_layernorm_gb_bwd": [P, I, L, P, L, P, P, P, P, I, I, P, L, P],
 }
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 
 def load_library():

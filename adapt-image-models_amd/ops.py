@@ -89,7 +89,7 @@ def gemm(a: torch.Tensor, w: torch.Tensor, epi: int, out: torch.Tensor, *, bias=
          stride_w: int = 0, M: Optional[int] = None, N: Optional[int] = None, K: Optional[int] = None,
          lda: Optional[int] = None, ldw: Optional[int] = None, ldv: Optional[int] = None, n_split: int = 0,
          act2: int = 0, xrow=None, reserve_cus: int = 0, probe=None, aux_grad: bool = False, aux_frag: bool = False,
-         slot_stride: int = 0):
+         slot_stride: int = 0, small_tile: bool = False):
     """``out = epilogue(a @ w.T)``; ``a`` is ``[M, K]`` (row stride ``lda``), ``w`` is ``[N, K]``."""
     lib = load_library()
     _chk(a, BF16, "a"); _chk(w, BF16, "w")
@@ -124,6 +124,7 @@ def gemm(a: torch.Tensor, w: torch.Tensor, epi: int, out: torch.Tensor, *, bias=
     g.ldx = xrow.stride(0) if xrow is not None else 0
     g.reserve_cus = int(reserve_cus)       # per-call: CUs this persistent launch leaves to other streams
     g.aux_grad = int(bool(aux_grad))       # ACT: out2 = act'(pre) instead of pre; DACT: aux holds act'(pre)
+    g.small_tile = int(bool(small_tile))   # the 64 x 64 kernel at any M: the large kernel's K order (aim_gemm_args.small_tile)
     g.aux_frag = int(bool(aux_frag))       # ACT / DACT: out2 / aux is a fragment-ordered buffer (frag_buffer)
     if aux_frag:
         t_ = out2 if epi == EPI_ACT else aux
@@ -254,7 +255,8 @@ def layernorm_fwd(x, gamma, beta, rows, D, ldx, *, y_bf16=None, y_f32=None, ldy=
 
 
 def layernorm_bwd(dy, x, gamma, mean, rstd, rows, D, *, lddy, ldx, lddx, dres=None, dx=None, dx_bf16=None,
-                  dgamma=None, dbeta=None):
+                  dgamma=None, dbeta=None, lddres=None):
+    """``lddres``: row stride of ``dres`` (default: ``lddx``, the rows of ``dx``)."""
     for n_, t_ in (("x", x), ("gamma", gamma), ("mean", mean), ("rstd", rstd),
                    ("dx", dx), ("dgamma", dgamma), ("dbeta", dbeta)):
         _chk(t_, F32, n_)
@@ -264,7 +266,8 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, rows, D, *, lddy, ldx, lddx, dres=No
         _chk(dres, dres.dtype if dres.dtype in (F32, BF16) else F32, "dres")
     check(load_library().aim_layernorm_bwd(dy.data_ptr(), int(dy.dtype == BF16), lddy, x.data_ptr(), ldx, gamma.data_ptr(),
                                            mean.data_ptr(), rstd.data_ptr(), _p(dres),
-                                           int(dres is not None and dres.dtype == BF16), _p(dx), _p(dx_bf16), lddx,
+                                           int(dres is not None and dres.dtype == BF16),
+                                           lddx if lddres is None else lddres, _p(dx), _p(dx_bf16), lddx,
                                            _p(dgamma), _p(dbeta), rows, D, _stream()), "aim_layernorm_bwd")
 
 
@@ -296,6 +299,21 @@ def attn_bwd(qkv, out, dout, lse, delta, dqkv, BT, N, H):
     _chk(lse, F32, "lse"); _chk(delta, F32, "delta")
     check(load_library().aim_attn_bwd(qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(),
                                       delta.data_ptr(), dqkv.data_ptr(), BT, N, H, _stream()), "aim_attn_bwd")
+
+
+def attn_fwd_cls(qkv, out_cls, lse_cls, BT, N, H):
+    """attn_fwd for the class query of every (frame, head) alone: out_cls [BT, D], lse_cls [BT, H]."""
+    _chk(qkv, BF16, "qkv"); _chk(out_cls, BF16, "out_cls"); _chk(lse_cls, F32, "lse_cls")
+    check(load_library().aim_attn_fwd_cls(qkv.data_ptr(), out_cls.data_ptr(), lse_cls.data_ptr(), BT, N, H, _stream()),
+          "aim_attn_fwd_cls")
+
+
+def attn_bwd_cls(qkv, out_cls, dout_cls, lse_cls, dqkv, BT, N, H):
+    """attn_bwd where only the class row of dout is non-zero: writes the whole dqkv [BT*N, 3D] (zeros in the other dq rows)."""
+    _chk(qkv, BF16, "qkv"); _chk(out_cls, BF16, "out_cls"); _chk(dout_cls, BF16, "dout_cls"); _chk(dqkv, BF16, "dqkv")
+    _chk(lse_cls, F32, "lse_cls")
+    check(load_library().aim_attn_bwd_cls(qkv.data_ptr(), out_cls.data_ptr(), dout_cls.data_ptr(), lse_cls.data_ptr(),
+                                          dqkv.data_ptr(), BT, N, H, _stream()), "aim_attn_bwd_cls")
 
 
 def cls_attn_fwd(qkv, out_cls, probs, B, T, N, H):

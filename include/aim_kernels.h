@@ -32,7 +32,7 @@ extern "C" {
 
 typedef uint16_t aim_bf16;
 
-#define AIM_ABI_VERSION 8
+#define AIM_ABI_VERSION 9
 
 int aim_version(void);                /* == AIM_ABI_VERSION */
 const char* aim_last_error(void);     /* message of the last failing call on this thread */
@@ -122,6 +122,11 @@ typedef struct aim_gemm_args {
        itself when it peels the thin last tile round of a large launch into a second, low-latency launch (AIM_GEMM_PEEL);
        the small-tile kernels honour it, the persistent 256 x 256 kernel requires 0. */
     int32_t row0;
+    /* != 0 (ABI 9; bf16 GEMM, K % 64 == 0, not EXPSUM): run this launch on the 64 x 64 kernel whatever M is.  That kernel
+       walks K in the persistent 256 x 256 kernel's order with the same epilogue arithmetic, so a launch over a SUBSET of the
+       rows of a large problem gives those rows the bits the large launch gives them (the 128 x 128 kernel that M < 1024
+       otherwise selects sums K in another order).  The last block's class-row launches set it. */
+    int32_t small_tile;
 } aim_gemm_args;
 
 int aim_gemm_bf16(const aim_gemm_args* args, int epilogue, int batch, void* stream);
@@ -174,7 +179,8 @@ int aim_layernorm_fwd_x16(const aim_bf16* x, int64_t ldx, const float* gamma, co
                           float* y_f32, uint8_t* y_fp8, int64_t ldy, int rows, int D, float eps, void* stream);
 int aim_layernorm_bwd(const void* dy, int dy_is_bf16 /* dy is bf16 (1) or f32 (0) */, int64_t lddy,
                       const float* x, int64_t ldx, const float* gamma,
-                      const float* mean, const float* rstd, const void* dres, int dres_is_bf16, float* dx,
+                      const float* mean, const float* rstd, const void* dres, int dres_is_bf16,
+                      int64_t lddres /* row stride of dres (ABI 9; it shared lddx before) */, float* dx,
                       aim_bf16* dx_bf16, int64_t lddx, float* dgamma, float* dbeta,
                       int rows, int D, void* stream);
 /* The bf16 form of aim_layernorm_bwd (dy, dres, dx all bf16, rows = frames*ntok) that also emits per-frame weighted column
@@ -198,6 +204,14 @@ int aim_attn_fwd_fp8(const aim_bf16* qkv, uint8_t* out_fp8, float* lse, int BT, 
 int aim_attn_bwd(const aim_bf16* qkv, const aim_bf16* out, const aim_bf16* dout, const float* lse,
                  float* delta /* scratch [BT, H, N] f32 */, aim_bf16* dqkv, int BT, int N, int H,
                  void* stream);
+/* The class query (token 0) of every (frame, head) only (ABI 9): the last block of the backbone, whose other rows nobody
+ * reads.  fwd: out_cls [BT, D] bf16, lse_cls [BT, H] f32 -- row 0 of aim_attn_fwd's results, bit for bit.
+ * bwd: from dout_cls [BT, D] (the gradient of every other row of the attention output is zero) WRITES the whole
+ * dqkv [BT*N, 3*D]: dk, dv of every key, dq in the class rows, zeros in every other dq row.  The q part of the other rows of
+ * qkv is not read.  Same shapes as aim_attn_fwd (N <= 288, 64-wide heads); fixed summation order, no atomics. */
+int aim_attn_fwd_cls(const aim_bf16* qkv, aim_bf16* out_cls, float* lse_cls, int BT, int N, int H, void* stream);
+int aim_attn_bwd_cls(const aim_bf16* qkv, const aim_bf16* out_cls, const aim_bf16* dout_cls, const float* lse_cls,
+                     aim_bf16* dqkv, int BT, int N, int H, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Temporal attention over the T class tokens of each clip -- vit_clip.py:220-224 with
