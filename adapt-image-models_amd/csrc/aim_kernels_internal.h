@@ -25,3 +25,25 @@ static inline bool aim_expsum_use256(int M, int N) {
     static const bool on = [] { const char* e = getenv("AIM_EXPSUM_256"); return !e || atoi(e) != 0; }();
     return on && (M > 128 || N > 128) && M <= 256 && N <= 256;
 }
+
+// Head-shifted spatial attention (aim_attn_fwd_shift / aim_attn_bwd_shift): the queries of frame b T + t see, in head h, the K
+// and V of frame b T + (t - s_h) mod T of the same clip.  The table travels in the kernel arguments, one byte per head,
+// already reduced to [0, T): no device memory, no allocation, nothing kept between calls.  T == 0: no shift.
+struct AttnShift {
+    unsigned long long lo, hi;          // heads 0..7, 8..15
+    int T;
+};
+// checks (B T == BT, H <= 16, T <= 256, |s_h| < T) and packs; nonzero: the error is set
+int aim_attn_shift_pack(const char* who, AttnShift* sh, const int* shifts, int B, int T, int BT, int H);
+#ifdef __HIPCC__
+__device__ __forceinline__ int attn_shift_of(const AttnShift& sh, int h) {
+    const unsigned long long w = h < 8 ? sh.lo : sh.hi;
+    return (int)((w >> ((h & 7) * 8)) & 0xff);
+}
+// the frame whose K / V (and dK / dV) belong to the queries of frame bt in head h; t = bt mod T
+__device__ __forceinline__ int attn_kv_frame_t(const AttnShift& sh, int bt, int t, int h) {
+    const int s = attn_shift_of(sh, h);
+    return bt - s + (t < s ? sh.T : 0);
+}
+__device__ __forceinline__ int attn_kv_frame(const AttnShift& sh, int bt, int h) { return attn_kv_frame_t(sh, bt, bt % sh.T, h); }
+#endif

@@ -34,10 +34,14 @@ constexpr float C2 = 0.125f * LOG2E;      // 1/sqrt(dh) * log2(e): probabilities
 // K^T row put NaN into dQ.  With p <= 1 the dS of such a key is finite and its zero K^T row removes it, as designed.
 __device__ __forceinline__ float prob_exp2(float x) { return __builtin_amdgcn_fmed3f(__builtin_amdgcn_exp2f(x), 0.f, 1.f); }
 
+// SHIFT (all three kernels of this file's full backward): the head-shifted form, aim_attn_bwd_shift.  An item is still the
+// QUERIES of (frame bt, head h); its K and V are read from frame attn_kv_frame(sh, bt, h) of the same clip and its dK and dV are
+// written there.  For a fixed head the map is a bijection on the clip's frames: every dK / dV row has one writer, as before.
+template <bool SHIFT>
 __global__ __launch_bounds__(512, 4) void attn_bwd_dq_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ out,
                                                           const bf16_t* __restrict__ dout, const float* __restrict__ lse,
                                                           float* __restrict__ delta, bf16_t* __restrict__ dqkv, int N,
-                                                          int H, int nkt) {
+                                                          int H, int nkt, const AttnShift sh) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     AIM_LDS char* sK = (AIM_LDS char*)smem_raw;
     AIM_LDS char* sV = sK + nkt * 16 * 128;
@@ -50,8 +54,9 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_dq_kernel(const bf16_t* __res
     const int frow = lane & 15, fq = lane >> 4;
     const bf16_t* base = qkv + (long long)bt * N * ld + h * 64;
     {
-        __amdgpu_buffer_rsrc_t rK = make_rsrc(base + D, ((long long)(N - 1) * ld + 64) * 2);
-        __amdgpu_buffer_rsrc_t rV = make_rsrc(base + 2 * D, ((long long)(N - 1) * ld + 64) * 2);
+        const bf16_t* kvb = SHIFT ? qkv + (long long)attn_kv_frame(sh, bt, h) * N * ld + h * 64 : base;
+        __amdgpu_buffer_rsrc_t rK = make_rsrc(kvb + D, ((long long)(N - 1) * ld + 64) * 2);
+        __amdgpu_buffer_rsrc_t rV = make_rsrc(kvb + 2 * D, ((long long)(N - 1) * ld + 64) * 2);
         const int srow = lane >> 3, schunk = (lane & 7) ^ srow;
         for (int p = wave; p < nkt * 2; p += 8) {
             const int key = p * 8 + srow;
@@ -139,9 +144,10 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_dq_kernel(const bf16_t* __res
     }
 }
 
+template <bool SHIFT>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dout,
                                                            const float* __restrict__ lse, const float* __restrict__ delta,
-                                                           bf16_t* __restrict__ dqkv, int N, int H, int nq32) {
+                                                           bf16_t* __restrict__ dqkv, int N, int H, int nq32, const AttnShift sh) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     AIM_LDS char* sQ = (AIM_LDS char*)smem_raw;
     AIM_LDS char* sO = sQ + nq32 * 128;
@@ -156,6 +162,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const bf16_t* __re
     const int frow = lane & 15, fq = lane >> 4;
     const bf16_t* base = qkv + (long long)bt * N * ld + h * 64;
     const bf16_t* dob = dout + (long long)bt * N * D + h * 64;
+    const int kvbt = SHIFT ? attn_kv_frame(sh, bt, h) : bt;       // the frame of the item's keys: K, V read and dK, dV written there
+    const bf16_t* kvb = SHIFT ? qkv + (long long)kvbt * N * ld + h * 64 : base;
     {
         __amdgpu_buffer_rsrc_t rQ = make_rsrc(base, ((long long)(N - 1) * ld + 64) * 2);
         __amdgpu_buffer_rsrc_t rO = make_rsrc(dob, ((long long)(N - 1) * D + 64) * 2);
@@ -182,8 +190,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const bf16_t* __re
             const int kc = key < N ? key : N - 1;
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-                kf[u][ks] = *(const bf16x8*)(base + (long long)kc * ld + D + (ks * 4 + fq) * 8);
-                vf[u][ks] = *(const bf16x8*)(base + (long long)kc * ld + 2 * D + (ks * 4 + fq) * 8);
+                kf[u][ks] = *(const bf16x8*)(kvb + (long long)kc * ld + D + (ks * 4 + fq) * 8);
+                vf[u][ks] = *(const bf16x8*)(kvb + (long long)kc * ld + 2 * D + (ks * 4 + fq) * 8);
             }
         }
         f32x4 dk[4][2], dv[4][2];
@@ -282,7 +290,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const bf16_t* __re
         for (int u = 0; u < 2; ++u) {
             const int key = kp * 32 + u * 16 + frow;
             // 16-byte stores: tiles (dt, dt+1) paired across even / odd 16-lane rows (aim_common.h pair_rows16)
-            bf16_t* op = dqkv + ((long long)bt * N + (key < N ? key : 0)) * ld + h * 64 + ((fq & 1) ? 16 + (fq - 1) * 4 : fq * 4);
+            bf16_t* op = dqkv + ((long long)kvbt * N + (key < N ? key : 0)) * ld + h * 64 + ((fq & 1) ? 16 + (fq - 1) * 4 : fq * 4);
 #pragma unroll
             for (int dt = 0; dt < 4; dt += 2) {
                 const bf16x8 vk = pair_rows16(
@@ -329,6 +337,7 @@ constexpr int PF_SLOT = 2 * 64 * 128;            // one ring slot: Q chunk [64][
 
 struct PfPos {                                   // a tick's item: workgroup-local index, query block, frame, head
     int k, qb, bt, h;
+    int t;                                       // SHIFT only: the frame inside its clip, bt mod T (advanced with bt, no division)
 };
 
 // XT ("extra tile"): N = 64 j + r with 1 <= r <= 16 and j >= 2 (197 = 3 x 64 + 5).  The r left-over queries would cost a
@@ -336,10 +345,14 @@ struct PfPos {                                   // a tick's item: workgroup-loc
 // with the item's LAST chunk as a fifth 16-query tile -- their Q / dO rows, L / delta and dS image live in small
 // single-buffered LDS areas beside the ring (written and read once per item, three ticks apart), the producers run one more
 // half step on them, and their dQ goes to waves 2 and 3.
-template <bool XT>
+// SHIFT: the item's K image and V fragments (the look-ahead of the NEXT item included) come from frame kvf(item) and its dK /
+// dV go there; chunks of Q / dO, delta, L and dQ stay in the item's own frame.  kvf is three scalar instructions on the
+// position's SGPRs (bt, t, h) and the table in the kernel arguments.
+template <bool XT, bool SHIFT>
 __global__ __launch_bounds__(512) void attn_bwd_pipe_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ out,
                                                             const bf16_t* __restrict__ dout, const float* __restrict__ lse,
-                                                            bf16_t* __restrict__ dqkv, int N, int H, int nkb, int items
+                                                            bf16_t* __restrict__ dqkv, int N, int H, int nkb, int items,
+                                                            const AttnShift sh
 #ifdef AIM_X_STAMPS
                                                             , unsigned long long* stamps
 #endif
@@ -376,6 +389,7 @@ __global__ __launch_bounds__(512) void attn_bwd_pipe_kernel(const bf16_t* __rest
     const int nit = ((int)items - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
     const int nt = nit * nqb;
     const int gbt = (int)gridDim.x / H, gh = (int)gridDim.x - gbt * H;      // item stride of the workgroup as (frames, heads)
+    const int gtm = SHIFT ? gbt % sh.T : 0;                                 // SHIFT: the frame stride inside a clip
 
     auto advance = [&](PfPos& p) {
         if (++p.qb == nqb) {
@@ -384,20 +398,28 @@ __global__ __launch_bounds__(512) void attn_bwd_pipe_kernel(const bf16_t* __rest
 #ifdef AIM_X_FWDROWS
             p.bt += gbt;
             p.h += gh;
+            if constexpr (SHIFT) p.t += gtm;
             if (p.h >= H) {
                 p.h -= H;
                 ++p.bt;
+                if constexpr (SHIFT) ++p.t;
             }
+            if constexpr (SHIFT) p.t -= p.t >= sh.T ? sh.T : 0;
 #else
             p.bt -= gbt;        // the items are walked from the LAST (frame, head) down (aim_common.h, AIM_REV_BLOCK)
             p.h -= gh;
+            if constexpr (SHIFT) p.t -= gtm;
             if (p.h < 0) {
                 p.h += H;
                 --p.bt;
+                if constexpr (SHIFT) --p.t;
             }
+            if constexpr (SHIFT) p.t += p.t < 0 ? sh.T : 0;
 #endif
         }
     };
+    // frame of an item's K, V, dK, dV
+    auto kvf = [&](const PfPos& p) { if constexpr (SHIFT) return attn_kv_frame_t(sh, p.bt, p.t, p.h); else return p.bt; };
     f32x4 acc[16];                     // producers: dK / dV of their 32 keys
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -479,7 +501,7 @@ __global__ __launch_bounds__(512) void attn_bwd_pipe_kernel(const bf16_t* __rest
         }
     };
     auto issue_kimg = [&](const PfPos& p) {
-        const bf16_t* base = qkv + (long long)p.bt * N * ld + p.h * 64;
+        const bf16_t* base = qkv + (long long)kvf(p) * N * ld + p.h * 64;
         const aim_rsrc_words rK = make_rsrc_words(base + D, ((long long)(N - 1) * ld + 64) * 2);
         AIM_LDS char* img = sKimg + (p.k & 1) * nrow * 128;
         for (int pc = wave; pc < nrow / 8; pc += 8) {
@@ -488,7 +510,7 @@ __global__ __launch_bounds__(512) void attn_bwd_pipe_kernel(const bf16_t* __rest
         }
     };
     auto issue_v = [&](const PfPos& p) {        // producers: V row fragments of an item -> vfn
-        const bf16_t* base = qkv + (long long)p.bt * N * ld + p.h * 64;
+        const bf16_t* base = qkv + (long long)kvf(p) * N * ld + p.h * 64;
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             const int key = wave * 32 + u * 16 + frow;
@@ -502,7 +524,7 @@ __global__ __launch_bounds__(512) void attn_bwd_pipe_kernel(const bf16_t* __rest
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             const int key = wave * 32 + u * 16 + frow;
-            bf16_t* op = dqkv + ((long long)p.bt * N + (key < N ? key : 0)) * ld + p.h * 64 + ((fq & 1) ? 16 + (fq - 1) * 4 : fq * 4);
+            bf16_t* op = dqkv + ((long long)kvf(p) * N + (key < N ? key : 0)) * ld + p.h * 64 + ((fq & 1) ? 16 + (fq - 1) * 4 : fq * 4);
 #pragma unroll
             for (int dt = 0; dt < 4; dt += 2) {
                 const f32x4 k0 = acc[dt * 2 + u] * 0.125f, k1 = acc[(dt + 1) * 2 + u] * 0.125f;
@@ -562,7 +584,7 @@ __global__ __launch_bounds__(512) void attn_bwd_pipe_kernel(const bf16_t* __rest
     };
 
     // positions of ticks T-1, T, T+1, T+2
-    PfPos prv{0, 0, 0, 0}, cur, nx1, nx2;
+    PfPos prv{0, 0, 0, 0, 0}, cur, nx1, nx2;
     cur.k = 0;
     cur.qb = 0;
 #ifdef AIM_X_FWDROWS
@@ -572,6 +594,7 @@ __global__ __launch_bounds__(512) void attn_bwd_pipe_kernel(const bf16_t* __rest
 #endif
     cur.bt = first / H;
     cur.h = first - cur.bt * H;
+    cur.t = SHIFT ? cur.bt % sh.T : 0;
     nx1 = cur;
     advance(nx1);
     nx2 = nx1;
@@ -994,12 +1017,11 @@ extern "C" int aim_attn_bwd_cls(const aim_bf16* qkv, const aim_bf16* out_cls, co
     return 0;
 }
 
-// workspace-free: delta is written into the caller-provided `delta` buffer ([BT, H, N] f32)
-extern "C" int aim_attn_bwd(const aim_bf16* qkv, const aim_bf16* out, const aim_bf16* dout, const float* lse,
-                            float* delta, aim_bf16* dqkv, int BT, int N, int H, void* stream) {
-    AIM_CHECK_ARG(BT > 0 && N > 0 && H > 0 && N <= 288, "attn_bwd: unsupported shape BT=%d N=%d H=%d (N <= 288)", BT, N, H);
-    AIM_CHECK_ARG(qkv && out && dout && lse && delta && dqkv, "attn_bwd: null pointer");
-    hipStream_t st = (hipStream_t)stream;
+namespace {
+
+template <bool SHIFT>
+int attn_bwd_launch(const aim_bf16* qkv, const aim_bf16* out, const aim_bf16* dout, const float* lse, float* delta, aim_bf16* dqkv,
+                    int BT, int N, int H, hipStream_t st, const AttnShift& sh) {
     // 65 <= N <= 224 (ViT-B/16's 197 tokens): the pipelined fused kernel; AIM_ATTN_BWD_PIPE=0 selects the two-kernel form.
     // Measured on MI355X (512 x 12 x 197 x 64, stand-alone): 0.39 ms against 0.54 ms; whole training step 53.8 against 54.7 ms.
     static const bool pipe_on = [] { const char* e = getenv("AIM_ATTN_BWD_PIPE"); return !e || atoi(e) != 0; }();
@@ -1011,8 +1033,8 @@ extern "C" int aim_attn_bwd(const aim_bf16* qkv, const aim_bf16* out, const aim_
         const int lds = 2 * PF_SLOT + 4 * nrow * 128 + 2 * 128 * 4 + (xt ? 4096 + nrow * 32 + 128 : 0);
         static bool attr_set2 = false;
         if (!attr_set2) {
-            (void)hipFuncSetAttribute((const void*)attn_bwd_pipe_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void*)attn_bwd_pipe_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            (void)hipFuncSetAttribute((const void*)attn_bwd_pipe_kernel<false, SHIFT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            (void)hipFuncSetAttribute((const void*)attn_bwd_pipe_kernel<true, SHIFT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             attr_set2 = true;
         }
         const int items = BT * H;
@@ -1030,29 +1052,49 @@ extern "C" int aim_attn_bwd(const aim_bf16* qkv, const aim_bf16* out, const aim_
         if (grid_cap > 0 && grid_cap < cus) cus = grid_cap;
         const int grid = items < cus ? items : cus;
         if (xt)
-            hipLaunchKernelGGL(attn_bwd_pipe_kernel<true>, dim3(grid), dim3(512), lds, st, (const bf16_t*)qkv, (const bf16_t*)out,
-                               (const bf16_t*)dout, lse, (bf16_t*)dqkv, N, H, nkb, items
+            hipLaunchKernelGGL((attn_bwd_pipe_kernel<true, SHIFT>), dim3(grid), dim3(512), lds, st, (const bf16_t*)qkv, (const bf16_t*)out,
+                               (const bf16_t*)dout, lse, (bf16_t*)dqkv, N, H, nkb, items, sh
 #ifdef AIM_X_STAMPS
                                , (unsigned long long*)delta
 #endif
             );
         else
-            hipLaunchKernelGGL(attn_bwd_pipe_kernel<false>, dim3(grid), dim3(512), lds, st, (const bf16_t*)qkv, (const bf16_t*)out,
-                               (const bf16_t*)dout, lse, (bf16_t*)dqkv, N, H, nkb, items
+            hipLaunchKernelGGL((attn_bwd_pipe_kernel<false, SHIFT>), dim3(grid), dim3(512), lds, st, (const bf16_t*)qkv, (const bf16_t*)out,
+                               (const bf16_t*)dout, lse, (bf16_t*)dqkv, N, H, nkb, items, sh
 #ifdef AIM_X_STAMPS
                                , (unsigned long long*)delta
 #endif
             );
-        AIM_CHECK_LAUNCH("aim_attn_bwd(pipelined)");
+        AIM_CHECK_LAUNCH(SHIFT ? "aim_attn_bwd_shift(pipelined)" : "aim_attn_bwd(pipelined)");
         return 0;
     }
     const int nkt = ((N + 31) / 32) * 2;   // 16-key tiles, even
     const int nq32 = ((N + 31) / 32) * 32;
-    hipLaunchKernelGGL(attn_bwd_dq_kernel, dim3(BT * H), dim3(512), nkt * 16 * 128 * 2, st, (const bf16_t*)qkv,
-                       (const bf16_t*)out, (const bf16_t*)dout, lse, delta, (bf16_t*)dqkv, N, H, nkt);
-    AIM_CHECK_LAUNCH("aim_attn_bwd(dq)");
-    hipLaunchKernelGGL(attn_bwd_dkv_kernel, dim3(BT * H), dim3(256), nq32 * 128 * 2 + nq32 * 8, st, (const bf16_t*)qkv,
-                       (const bf16_t*)dout, lse, delta, (bf16_t*)dqkv, N, H, nq32);
-    AIM_CHECK_LAUNCH("aim_attn_bwd(dkv)");
+    hipLaunchKernelGGL(attn_bwd_dq_kernel<SHIFT>, dim3(BT * H), dim3(512), nkt * 16 * 128 * 2, st, (const bf16_t*)qkv,
+                       (const bf16_t*)out, (const bf16_t*)dout, lse, delta, (bf16_t*)dqkv, N, H, nkt, sh);
+    AIM_CHECK_LAUNCH(SHIFT ? "aim_attn_bwd_shift(dq)" : "aim_attn_bwd(dq)");
+    hipLaunchKernelGGL(attn_bwd_dkv_kernel<SHIFT>, dim3(BT * H), dim3(256), nq32 * 128 * 2 + nq32 * 8, st, (const bf16_t*)qkv,
+                       (const bf16_t*)dout, lse, delta, (bf16_t*)dqkv, N, H, nq32, sh);
+    AIM_CHECK_LAUNCH(SHIFT ? "aim_attn_bwd_shift(dkv)" : "aim_attn_bwd(dkv)");
     return 0;
+}
+
+}  // namespace
+
+// workspace-free: delta is written into the caller-provided `delta` buffer ([BT, H, N] f32)
+extern "C" int aim_attn_bwd(const aim_bf16* qkv, const aim_bf16* out, const aim_bf16* dout, const float* lse,
+                            float* delta, aim_bf16* dqkv, int BT, int N, int H, void* stream) {
+    AIM_CHECK_ARG(BT > 0 && N > 0 && H > 0 && N <= 288, "attn_bwd: unsupported shape BT=%d N=%d H=%d (N <= 288)", BT, N, H);
+    AIM_CHECK_ARG(qkv && out && dout && lse && delta && dqkv, "attn_bwd: null pointer");
+    return attn_bwd_launch<false>(qkv, out, dout, lse, delta, dqkv, BT, N, H, (hipStream_t)stream, AttnShift{});
+}
+
+extern "C" int aim_attn_bwd_shift(const aim_bf16* qkv, const aim_bf16* out, const aim_bf16* dout, const float* lse,
+                                  float* delta, aim_bf16* dqkv, int BT, int N, int H, int B, int T, const int* shifts,
+                                  void* stream) {
+    AIM_CHECK_ARG(BT > 0 && N > 0 && H > 0 && N <= 288, "attn_bwd_shift: unsupported shape BT=%d N=%d H=%d (N <= 288)", BT, N, H);
+    AIM_CHECK_ARG(qkv && out && dout && lse && delta && dqkv, "attn_bwd_shift: null pointer");
+    AttnShift sh;
+    if (int rc = aim_attn_shift_pack("attn_bwd_shift", &sh, shifts, B, T, BT, H)) return rc;
+    return attn_bwd_launch<true>(qkv, out, dout, lse, delta, dqkv, BT, N, H, (hipStream_t)stream, sh);
 }

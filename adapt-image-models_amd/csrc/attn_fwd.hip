@@ -32,9 +32,11 @@ namespace {
 // are staged as always, the first 16-query tile runs and query row 0 is stored: out [BT, D], lse [BT, H].  The arithmetic
 // of that row is the full kernel's (a query is one MFMA column and one lane quartet: the tile's other queries do not
 // touch it, whatever they hold).
-template <int NKT, int NFULL, bool OUT8 = false, bool CLS = false>
+// SHIFT: head-shifted form (aim_attn_fwd_shift): K and V of the item come from frame attn_kv_frame(sh, bt, h) of the same clip;
+// the queries, the output and the log-sum-exp stay in frame bt.  Only the staging base differs.
+template <int NKT, int NFULL, bool OUT8 = false, bool CLS = false, bool SHIFT = false>
 __global__ __launch_bounds__(512, 4) void attn_fwd_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
-                                                          float* __restrict__ lse, int N, int H
+                                                          float* __restrict__ lse, int N, int H, const AttnShift sh
 #ifdef AIM_X_STAMPS
                                                           , unsigned long long* probe
 #endif
@@ -69,8 +71,9 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_kernel(const bf16_t* __restri
         for (int ks = 0; ks < 2; ++ks) qf[ks] = *(const bf16x8*)(base + (long long)qc * ld + (ks * 4 + fq) * 8);
     }
     {
-        __amdgpu_buffer_rsrc_t rK = make_rsrc(base + D, ((long long)(N - 1) * ld + 64) * 2);
-        __amdgpu_buffer_rsrc_t rV = make_rsrc(base + 2 * D, ((long long)(N - 1) * ld + 64) * 2);
+        const bf16_t* kvb = SHIFT ? qkv + (long long)attn_kv_frame(sh, bt, h) * N * ld + h * 64 : base;
+        __amdgpu_buffer_rsrc_t rK = make_rsrc(kvb + D, ((long long)(N - 1) * ld + 64) * 2);
+        __amdgpu_buffer_rsrc_t rV = make_rsrc(kvb + 2 * D, ((long long)(N - 1) * ld + 64) * 2);
         const int srow = lane >> 3, schunk = (lane & 7) ^ srow;
         for (int p = wave; p < NKT * 2; p += NW) {
             const int key = p * 8 + srow;
@@ -204,23 +207,23 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_kernel(const bf16_t* __restri
 #endif
 }
 
-template <int NKT, int NFULL, bool OUT8 = false, bool CLS = false>
-int launch_nf(const aim_bf16* qkv, aim_bf16* out, float* lse, int BT, int N, int H, hipStream_t st) {
-    hipLaunchKernelGGL((attn_fwd_kernel<NKT, NFULL, OUT8, CLS>), dim3(BT * H), dim3(512), NKT * 16 * 128 * 2, st, (const bf16_t*)qkv,
-                       (bf16_t*)out, lse, N, H
+template <int NKT, int NFULL, bool OUT8 = false, bool CLS = false, bool SHIFT = false>
+int launch_nf(const aim_bf16* qkv, aim_bf16* out, float* lse, int BT, int N, int H, hipStream_t st, const AttnShift& sh) {
+    hipLaunchKernelGGL((attn_fwd_kernel<NKT, NFULL, OUT8, CLS, SHIFT>), dim3(BT * H), dim3(512), NKT * 16 * 128 * 2, st, (const bf16_t*)qkv,
+                       (bf16_t*)out, lse, N, H, sh
 #ifdef AIM_X_STAMPS
                        , g_attn_probe
 #endif
     );
-    AIM_CHECK_LAUNCH(CLS ? "aim_attn_fwd_cls" : "aim_attn_fwd");
+    AIM_CHECK_LAUNCH(CLS ? "aim_attn_fwd_cls" : SHIFT ? "aim_attn_fwd_shift" : "aim_attn_fwd");
     return 0;
 }
 
 // masking code only on the last two key tiles when N reaches into them, on every tile otherwise
-template <int NKT, bool OUT8 = false, bool CLS = false>
-int launch(const aim_bf16* qkv, aim_bf16* out, float* lse, int BT, int N, int H, hipStream_t st) {
-    if ((N >> 4) >= NKT - 2) return launch_nf<NKT, NKT - 2, OUT8, CLS>(qkv, out, lse, BT, N, H, st);
-    return launch_nf<NKT, 0, OUT8, CLS>(qkv, out, lse, BT, N, H, st);
+template <int NKT, bool OUT8 = false, bool CLS = false, bool SHIFT = false>
+int launch(const aim_bf16* qkv, aim_bf16* out, float* lse, int BT, int N, int H, hipStream_t st, const AttnShift& sh = AttnShift{}) {
+    if ((N >> 4) >= NKT - 2) return launch_nf<NKT, NKT - 2, OUT8, CLS, SHIFT>(qkv, out, lse, BT, N, H, st, sh);
+    return launch_nf<NKT, 0, OUT8, CLS, SHIFT>(qkv, out, lse, BT, N, H, st, sh);
 }
 
 }  // namespace
@@ -233,6 +236,33 @@ extern "C" int aim_attn_fwd(const aim_bf16* qkv, aim_bf16* out, float* lse, int 
     if (N <= 64) return launch<4>(qkv, out, lse, BT, N, H, st);
     if (N <= 224) return launch<14>(qkv, out, lse, BT, N, H, st);
     return launch<18>(qkv, out, lse, BT, N, H, st);
+}
+
+int aim_attn_shift_pack(const char* who, AttnShift* sh, const int* shifts, int B, int T, int BT, int H) {
+    AIM_CHECK_ARG(shifts, "%s: null shift table", who);
+    AIM_CHECK_ARG(B > 0 && T > 0 && T <= 256 && H <= 16 && (long long)B * T == BT,
+                  "%s: unsupported shape B=%d T=%d BT=%d H=%d (B T == BT, T <= 256, H <= 16)", who, B, T, BT, H);
+    sh->lo = sh->hi = 0;
+    sh->T = T;
+    for (int h = 0; h < H; ++h) {
+        AIM_CHECK_ARG(shifts[h] > -T && shifts[h] < T, "%s: shift %d of head %d is outside (-T, T), T=%d", who, shifts[h], h, T);
+        const unsigned long long s = (unsigned long long)((shifts[h] + T) % T);
+        (h < 8 ? sh->lo : sh->hi) |= s << ((h & 7) * 8);
+    }
+    return 0;
+}
+
+extern "C" int aim_attn_fwd_shift(const aim_bf16* qkv, aim_bf16* out, float* lse, int BT, int N, int H, int B, int T,
+                                  const int* shifts, void* stream) {
+    AIM_CHECK_ARG(BT > 0 && N > 0 && H > 0 && N <= 288, "attn_fwd_shift: unsupported shape BT=%d N=%d H=%d (N <= 288)", BT, N, H);
+    AIM_CHECK_ARG(qkv && out && lse, "attn_fwd_shift: null pointer");
+    AttnShift sh;
+    if (int rc = aim_attn_shift_pack("attn_fwd_shift", &sh, shifts, B, T, BT, H)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (N <= 32) return launch<2, false, false, true>(qkv, out, lse, BT, N, H, st, sh);
+    if (N <= 64) return launch<4, false, false, true>(qkv, out, lse, BT, N, H, st, sh);
+    if (N <= 224) return launch<14, false, false, true>(qkv, out, lse, BT, N, H, st, sh);
+    return launch<18, false, false, true>(qkv, out, lse, BT, N, H, st, sh);
 }
 
 extern "C" int aim_attn_fwd_cls(const aim_bf16* qkv, aim_bf16* out_cls, float* lse_cls, int BT, int N, int H, void* stream) {

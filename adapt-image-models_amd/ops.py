@@ -301,6 +301,31 @@ def attn_bwd(qkv, out, dout, lse, delta, dqkv, BT, N, H):
                                       delta.data_ptr(), dqkv.data_ptr(), BT, N, H, _stream()), "aim_attn_bwd")
 
 
+def _shift_table(shifts, H):
+    """H ints for aim_attn_*_shift (host memory, read during the call): a shorter table leaves the remaining heads unshifted"""
+    import ctypes
+    s = [int(x) for x in shifts]
+    if len(s) > H:
+        raise ValueError(f"{len(s)} shifts for {H} heads")
+    return (ctypes.c_int * H)(*(s + [0] * (H - len(s))))
+
+
+def attn_fwd_shift(qkv, out, lse, B, T, N, H, shifts):
+    """attn_fwd over B clips of T frames where head h reads the K / V of frame (t - shifts[h]) mod T of the same clip."""
+    _chk(qkv, BF16, "qkv"); _chk(out, BF16, "out"); _chk(lse, F32, "lse")
+    check(load_library().aim_attn_fwd_shift(qkv.data_ptr(), out.data_ptr(), lse.data_ptr(), B * T, N, H, B, T,
+                                            _shift_table(shifts, H), _stream()), "aim_attn_fwd_shift")
+
+
+def attn_bwd_shift(qkv, out, dout, lse, delta, dqkv, B, T, N, H, shifts):
+    """backward of attn_fwd_shift: dq in the query's frame, dk / dv in the frame the keys were read from."""
+    _chk(qkv, BF16, "qkv"); _chk(out, BF16, "out"); _chk(dout, BF16, "dout"); _chk(dqkv, BF16, "dqkv")
+    _chk(lse, F32, "lse"); _chk(delta, F32, "delta")
+    check(load_library().aim_attn_bwd_shift(qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(),
+                                            delta.data_ptr(), dqkv.data_ptr(), B * T, N, H, B, T,
+                                            _shift_table(shifts, H), _stream()), "aim_attn_bwd_shift")
+
+
 def attn_fwd_cls(qkv, out_cls, lse_cls, BT, N, H):
     """attn_fwd for the class query of every (frame, head) alone: out_cls [BT, D], lse_cls [BT, H]."""
     _chk(qkv, BF16, "qkv"); _chk(out_cls, BF16, "out_cls"); _chk(lse_cls, F32, "lse_cls")

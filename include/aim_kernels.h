@@ -32,7 +32,7 @@ extern "C" {
 
 typedef uint16_t aim_bf16;
 
-#define AIM_ABI_VERSION 9
+#define AIM_ABI_VERSION 10
 
 int aim_version(void);                /* == AIM_ABI_VERSION */
 const char* aim_last_error(void);     /* message of the last failing call on this thread */
@@ -212,6 +212,18 @@ int aim_attn_bwd(const aim_bf16* qkv, const aim_bf16* out, const aim_bf16* dout,
 int aim_attn_fwd_cls(const aim_bf16* qkv, aim_bf16* out_cls, float* lse_cls, int BT, int N, int H, void* stream);
 int aim_attn_bwd_cls(const aim_bf16* qkv, const aim_bf16* out_cls, const aim_bf16* dout_cls, const float* lse_cls,
                      aim_bf16* dqkv, int BT, int N, int H, void* stream);
+/* Head-shifted form (ABI 10; ViT_CLIP_ZEROI2V's HeadShift, vit_clip_zeroI2V.py): BT = B*T frames, clips of T consecutive
+ * frames.  In head h the queries of frame (b, t) attend to the K and V of frame (b, (t - shifts[h]) mod T) of the same clip --
+ * torch.roll(k, shifts[h], dims=t) -- q, out, lse and dout stay in frame (b, t).  bwd: dq in the query's frame; dk, dv are
+ * written to the frame the keys were read from (per head the map is a bijection on the clip: one writer per row, no atomics,
+ * nothing is summed across items).  shifts: H ints in HOST memory, |shifts[h]| < T, read during the call and passed to the
+ * kernels by value (H <= 16, T <= 256): nothing is allocated or kept.  Results are the bits of aim_attn_fwd / aim_attn_bwd on
+ * a qkv whose K and V columns were rolled that way (dk, dv rolled back); an all-zero table gives the unshifted bits. */
+int aim_attn_fwd_shift(const aim_bf16* qkv, aim_bf16* out, float* lse, int BT, int N, int H, int B, int T, const int* shifts,
+                       void* stream);
+int aim_attn_bwd_shift(const aim_bf16* qkv, const aim_bf16* out, const aim_bf16* dout, const float* lse,
+                       float* delta /* scratch [BT, H, N] f32 */, aim_bf16* dqkv, int BT, int N, int H, int B, int T,
+                       const int* shifts, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Temporal attention over the T class tokens of each clip -- vit_clip.py:220-224 with
