@@ -78,6 +78,19 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const TX* __restrict__ x, l
     }
 }
 
+// The last steps of one element of the LayerNorm backward in ONE fixed operation order, whatever the compiler would fuse in
+// the kernel around them: xhat * m2 folded into the subtraction (fma), the scale, then the residual as an addition of its own.
+// ln_bwd_kernel and ln_bwd_fsum_kernel both go through these, which is what makes their dx the same bits (left to the
+// compiler, one kernel fused rs * t + dres and all four xhat * m2, the other neither the first nor two of the four).
+__device__ __forceinline__ float ln_bwd_elem(float g, float xh, float m1, float m2, float rs) {
+#pragma clang fp contract(off)
+    return rs * __builtin_fmaf(-xh, m2, g - m1);
+}
+__device__ __forceinline__ f32x4 ln_add_res(f32x4 o, f32x4 r) {
+#pragma clang fp contract(off)
+    return o + r;
+}
+
 // dx = dres + rstd * (g - mean(g) - xhat * mean(g*xhat)),  g = dy * gamma
 template <int NC, typename TDY, typename TDR>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const TDY* __restrict__ dy, long long lddy,
@@ -112,7 +125,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const TDY* __restrict__ dy,
                 xh[c][e] = (xv[e] - mu) * rs;
                 g[c][e] = d[e] * gm[e];
                 s1 += g[c][e];
-                s2 += g[c][e] * xh[c][e];
+                s2 = __builtin_fmaf(g[c][e], xh[c][e], s2);
             }
             if (dgamma) {
 #pragma unroll
@@ -130,13 +143,13 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const TDY* __restrict__ dy,
         if (ch < nch) {
             f32x4 o;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = rs * (g[c][e] - m1 - xh[c][e] * m2);
+            for (int e = 0; e < 4; ++e) o[e] = ln_bwd_elem(g[c][e], xh[c][e], m1, m2, rs);
             if (dres) {
                 if constexpr (sizeof(TDR) == 4) {
-                    o += *(const f32x4*)(dres + (long long)row * lddres + ch * 4);
+                    o = ln_add_res(o, *(const f32x4*)(dres + (long long)row * lddres + ch * 4));
                 } else {
                     const bf16x4 rb = *(const bf16x4*)(dres + (long long)row * lddres + ch * 4);
-                    o += f32x4{(float)rb[0], (float)rb[1], (float)rb[2], (float)rb[3]};
+                    o = ln_add_res(o, f32x4{(float)rb[0], (float)rb[1], (float)rb[2], (float)rb[3]});
                 }
             }
             if (dx) *(f32x4*)(dx + (long long)row * lddx + ch * 4) = o;
@@ -194,7 +207,7 @@ __global__ __launch_bounds__(256, (NC <= 4 ? 6 : 2)) void ln_bwd_fsum_kernel(con
                     xh[c][e] = (xv[e] - mu) * rs;
                     gv[c][e] = d[e] * gm[e];
                     s1 += gv[c][e];
-                    s2 += gv[c][e] * xh[c][e];
+                    s2 = __builtin_fmaf(gv[c][e], xh[c][e], s2);
                 }
             }
         }
@@ -205,9 +218,9 @@ __global__ __launch_bounds__(256, (NC <= 4 ? 6 : 2)) void ln_bwd_fsum_kernel(con
             if (ch < nch) {
                 f32x4 o;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = rs * (gv[c][e] - m1 - xh[c][e] * m2);
+                for (int e = 0; e < 4; ++e) o[e] = ln_bwd_elem(gv[c][e], xh[c][e], m1, m2, rs);
                 const bf16x4 rb = *(const bf16x4*)(dres + row * lddx + ch * 4);
-                o += f32x4{(float)rb[0], (float)rb[1], (float)rb[2], (float)rb[3]};
+                o = ln_add_res(o, f32x4{(float)rb[0], (float)rb[1], (float)rb[2], (float)rb[3]});
                 const bf16x4 ob = pack4(o[0], o[1], o[2], o[3]);
                 *(bf16x4*)(dxb + row * lddx + ch * 4) = ob;
 #pragma unroll

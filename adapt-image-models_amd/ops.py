@@ -476,7 +476,7 @@ def embed_nopre_bwd(dx, B, T, N, D, *, dtok=None, dcls=None, dpos=None, dtempora
 def layernorm_gb_bwd(dy, x, mean, rstd, rows, D, dgamma, dbeta, *, lddy=None, ldx=None):
     """LayerNorm affine gradients over ``rows`` rows: dgamma += sum dy * (x - mean) * rstd, dbeta += sum dy (fp32, ADDED).
     Two-stage, fixed order: bitwise reproducible at any row count (aim_layernorm_bwd's own dgamma / dbeta use fp32 atomics
-    above 4 096 rows)."""
+    above 8 192 rows)."""
     _chk(dy, dy.dtype if dy.dtype in (F32, BF16) else F32, "dy")
     for n_, t_ in (("x", x), ("mean", mean), ("rstd", rstd), ("dgamma", dgamma), ("dbeta", dbeta)):
         _chk(t_, F32, n_)

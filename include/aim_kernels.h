@@ -164,7 +164,7 @@ int aim_wgrad_bias_bf16(const aim_bf16* G, int ldg, const aim_bf16* A, int lda, 
  * LayerNorm (fp32 statistics, eps inside rsqrt) -- vit_clip.py:71-77 (ln_1, ln_2, ln_pre, ln_post)
  *   fwd: y = (x - mean) * rstd * gamma + beta ; x fp32 rows with stride ldx; y as bf16 and/or f32
  *   bwd: dx = dres + rstd * (g - mean(g) - xhat * mean(g * xhat)), g = dy * gamma   (frozen gamma)
- *        optional: dgamma/dbeta accumulation for the trainable ln_post (rows <= 4096: one ordered column pass,
+ *        optional: dgamma/dbeta accumulation for the trainable ln_post (rows <= 8192: one ordered column pass,
  *        no atomics; more rows: per-element fp32 atomics).
  * ------------------------------------------------------------------------------------------ */
 int aim_layernorm_fwd(const float* x, int64_t ldx, const float* gamma, const float* beta,
@@ -309,8 +309,11 @@ int64_t aim_embed_bwd_workspace_bytes(int B, int T, int N, int D);
 /* ------------------------------------------------------------------------------------------
  * Small reductions / casts used by the block's backward and the optimizer boundary.
  *   frame_sum : out[frame][d] = sum_tok w[tok] * x[frame*ntok + tok][d]   (x f32, w may be NULL)
- *   colsum    : out[c] += sum_m rs(m) * X[m][c]   (X bf16; rs as in the GEMM; two-stage ordered reduction through
- *               the workspace, fp32 atomics only without one)
+ *   colsum    : out[c] += sum_m rs(m) * X[m][c]   (X bf16; rs as in the GEMM).  C % 8 == 0, ldx % 8 == 0, C <= 2048:
+ *               two-stage ordered reduction through the workspace (more than 64 rows and ceil(M / max(64, ceil(M/1024))) * C
+ *               floats of workspace); without one, M <= 2048 runs as one block in a fixed order and a larger M adds one
+ *               fp32 atomic per column per 64-row block.  Any other C or ldx: a scalar kernel that ignores the workspace and
+ *               adds one fp32 atomic per column per row block (not reproducible above 64 rows).
  *   cast      : f32 -> bf16 (optionally transposed [R,C] -> [C,R]) for weight staging
  *   scale_rows: y[r][c] = s[r] * x[r][c]  (f32 x -> bf16 y), used for lamda * crs_attn
  * ------------------------------------------------------------------------------------------ */
