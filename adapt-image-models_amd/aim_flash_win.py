@@ -1,0 +1,508 @@
+"""``AIM_FLASH_WIN`` backbone (AIM with a 3-D window temporal attention and a temporal class-token prompt) on the HIP kernels.
+
+Drop-in for ``mmaction/models/backbones/vitclip_aim_flash_win.py:276-433`` of the reference at ``wind_attn=True`` (what its four
+recipes, ``configs/recognition/vit/AIM/AIM_flash_win_base_*.py``, use): same registry name, constructor keywords, ``init_weights``
+policy, parameter names and shapes (``attn.Wqkv``, ``attn.out_proj``, ``mlp.fc1``, ``mlp.fc2`` of the reference's FlashMHA /
+FlashMlp containers: the usual q | k | v head-major layout, softmax(Q K^T / sqrt(dh)) V and fc1 -> QuickGELU -> fc2, whatever
+``use_flash_attn`` says), same ``forward(x[B,3,T,H,W]) -> [B,width,T,1,1]``.
+
+Per block (reference ``:146-225``), frame-major rows, N = G G + 1 tokens per frame, f1 f2 f3 the block's three DropPath draws:
+
+  1. xl = ln_1(x), qkv = xl Wqkv^T + b over ALL rows: ln_1 and the projection are token-wise, so one pass serves 2 and 3.
+  2. patch tokens: attention inside the (wt, wh, ww) windows of the [T, G, G] grid -- ``aim_win_attn_fwd`` on the fused qkv
+     buffer; window_partition / window_reverse are addresses inside the kernel, nothing is ever copied into window order.
+  3. class tokens: attention over the T class tokens of each clip -- ``aim_cls_attn_fwd`` on the same buffer.
+  4. ta = [3 | 2] Wo^T + bo (the reference's [cls_attn, windows_attn]);  x1 = x + f1[frame] T_Adapter(ta)   (no adapter scale)
+  5. (prompt) ta's class row becomes one more token of its frame: x' = [x1, prompt];
+     x2 = x' + attn(ln_1 x') + f2[frame] scale S_Adapter(x');  the prompt token is dropped.  This is zeroi2v.py's spatial step
+     without head shifts (``aim_attn_fwd`` at 198 tokens).  The prompt's own output is discarded but it is a key and a value
+     of every other token, so its gradient flows back into 3 through ta.
+  6. x3 = x2 + mlp(ln_2 x2) + f3[frame] scale MLP_Adapter(ln_2 x2)      (``_mlp_adapter_forward``)
+
+DropPath: x is [BT, n, d] when timm's DropPath sees it, so a draw has shape (BT, 1, 1) and drops FRAMES (``af`` of the GEMM
+epilogues; ViT_CLIP drops token positions).  Three draws per block with rate > 0, in the order 4, 5, 6.
+
+Layout: as in zeroi2v.py the residual stream keeps P = N + 1 token rows per frame through the whole stack when there is a
+prompt.  The extra row is a slot BEHIND the frame's tokens (row N; attention does not see an order among keys, and every
+other op is row-wise, so the reference's position 1 and this position N compute the same numbers): step 4's result is copied
+into it (B T rows), steps 5 and 6 run on all P rows, and the slot's value after step 6 is dead -- the next block overwrites
+it.  Its gradient row is extracted and zeroed once ln_1's backward of step 5 has produced it.  The window kernel takes the
+row stride P beside N, so the slot costs no copy of the other rows; only the embedding is copied into the P layout once.
+
+The reference's shifted branch (``not_shift=False``) rolls the windows back and then DISCARDS the result (``:188`` assigns
+``windows_attn``, ``:192`` rearranges ``shifted_win``): its output is mis-aligned by the shift.  It is not built.
+"""
+import logging
+from types import SimpleNamespace
+from typing import Dict, List, Optional
+
+import torch
+from torch import nn
+
+from . import ops
+from .backbone import (_ADAPTER_LEAVES, _ADAPTERS, _AUX_GRAD, _DP_RESERVE, BF16, F32, Adapter, LayerNorm, QuickGELU, ViT_CLIP,
+                       _AdapterW, _empty, _Fork, _Frozen, _mlp_adapter_backward, _mlp_adapter_forward)
+from .registry import BACKBONES
+from .zeroi2v import _wgrads_beside
+
+_LOG = logging.getLogger("aim_amd")
+
+
+def clip_window(window_size, T: int, G: int):
+    """the reference's ``get_window_size`` (:51-64): an extent that reaches the grid's is clipped to it"""
+    return tuple(min(int(w), x) for w, x in zip(window_size, (T, G, G)))
+
+
+class _MHA(nn.Module):
+    """Parameter container with the names of flash_attn's ``MHA`` (``Wqkv``, ``out_proj``)."""
+
+    def __init__(self, d_model: int):
+        super().__init__()
+        self.Wqkv = nn.Linear(d_model, 3 * d_model)
+        self.out_proj = nn.Linear(d_model, d_model)
+
+
+class _Mlp(nn.Module):
+    """Parameter container with the names of flash_attn's ``Mlp`` (``fc1``, ``fc2``)."""
+
+    def __init__(self, d_model: int):
+        super().__init__()
+        self.fc1 = nn.Linear(d_model, 4 * d_model)
+        self.activation = QuickGELU()
+        self.fc2 = nn.Linear(4 * d_model, d_model)
+
+
+class WinResidualAttentionBlock(nn.Module):
+    """Parameters of one block (reference :100-139); compute lives in ``_FlashWinFn``."""
+
+    def __init__(self, d_model: int, n_head: int, scale: float, num_frames: int, drop_path: float):
+        super().__init__()
+        self.attn = _MHA(d_model)
+        self.ln_1 = LayerNorm(d_model)
+        self.mlp = _Mlp(d_model)
+        self.ln_2 = LayerNorm(d_model)
+        self.n_head, self.d_model = n_head, d_model
+        self.MLP_Adapter = Adapter(d_model, skip_connect=False)
+        self.S_Adapter = Adapter(d_model, skip_connect=False)
+        self.scale = scale
+        self.T_Adapter = Adapter(d_model, skip_connect=False)
+        self.num_frames = num_frames
+        self.drop_prob = float(drop_path)
+
+
+class WinTransformer(nn.Module):
+    def __init__(self, num_frames, width, layers, heads, scale, drop_path):
+        super().__init__()
+        self.width, self.layers = width, layers
+        dpr = [x.item() for x in torch.linspace(0, drop_path, layers)]      # reference :235
+        self.resblocks = nn.Sequential(*[WinResidualAttentionBlock(width, heads, scale, num_frames, dpr[i]) for i in range(layers)])
+
+
+def _frozen_view(blk: WinResidualAttentionBlock):
+    """the block's frozen tensors under the names ``_Frozen`` reads (CLIP's nn.MultiheadAttention / c_fc / c_proj)"""
+    a = blk.attn
+    return SimpleNamespace(attn=SimpleNamespace(in_proj_weight=a.Wqkv.weight, in_proj_bias=a.Wqkv.bias, out_proj=a.out_proj),
+                           mlp=SimpleNamespace(c_fc=blk.mlp.fc1, c_proj=blk.mlp.fc2), ln_1=blk.ln_1, ln_2=blk.ln_2,
+                           d_model=blk.d_model, MLP_Adapter=blk.MLP_Adapter)
+
+
+def _block_forward(x, fz: _Frozen, adp: Dict[str, _AdapterW], B, T, N, P, H, window, f1, f2, f3, tokm, save: bool):
+    """x [B*T*P, D] f32 (P = N + 1 with the prompt: row N of every frame is its slot) -> x3, ctx.  f1, f2, f3 [B*T]: the
+    DropPath factors per frame (f2, f3 times the adapter scale); tokm [P]: 1 per token, 0 at the slot."""
+    dev = x.device
+    M, D = x.shape
+    BT, r = B * T, fz.r
+    prompt = P != N
+    xv = lambda t: t.view(BT, P, -1)
+    # ---- 1: ln_1 and the QKV projection over every row
+    xl = _empty((M, D), BF16, dev)
+    mean1, rstd1 = _empty((M,), F32, dev), _empty((M,), F32, dev)
+    ops.layernorm_fwd(x, fz.g1, fz.b1, M, D, D, y_bf16=xl, mean=mean1, rstd=rstd1)
+    qkv = _empty((M, 3 * D), BF16, dev)
+    ops.gemm(xl, fz.Wqkv, ops.EPI_BF16, qkv, bias=fz.bqkv)
+    del xl
+    # ---- 2, 3: window attention on the patch rows, class-token attention on the class rows, into one [M, D] buffer
+    at_ = _empty((M, D), BF16, dev)
+    lse_w = _empty((BT, H, P), F32, dev)
+    ops.win_attn_fwd(qkv, at_, lse_w, B, T, N, H, window, P=P)
+    ot, probs = _empty((BT, D), BF16, dev), _empty((B, H, T, T), F32, dev)
+    ops.cls_attn_fwd(qkv, ot, probs, B, T, P, H)
+    xv(at_)[:, 0] = ot
+    if prompt:
+        xv(at_)[:, N] = 0
+    # ---- 4: out_proj, T_Adapter, x1 = x + f1 (GELU(ta W1^T + b1) W2^T + b2)
+    ta = _empty((M, D), BF16, dev)
+    ops.gemm(at_, fz.Wo, ops.EPI_BF16, ta, bias=fz.bo)
+    tad = adp["T_Adapter"]
+    t_pre, t_hs = _empty((M, r), BF16, dev), _empty((M, r), BF16, dev)
+    ops.gemm(ta, tad.W1, ops.EPI_ACT, t_hs, bias=tad.b1, out2=t_pre, act=ops.ACT_GELU, af=f1, ntok=P, aux_grad=_AUX_GRAD)
+    x1 = _empty((M, D), F32, dev)
+    ops.gemm(t_hs, tad.W2, ops.EPI_F32, x1, resid=x, vec=f1.reshape(-1, 1) * tad.b2.reshape(1, -1), ldv=D, ntok=P)
+    # ---- 5: the prompt token, spatial attention over the P tokens of a frame, S_Adapter on the residual stream itself
+    if prompt:
+        xv(x1)[:, N] = xv(ta)[:, 0]
+    xl2 = _empty((M, D), BF16, dev)
+    mean1b, rstd1b = _empty((M,), F32, dev), _empty((M,), F32, dev)
+    ops.layernorm_fwd(x1, fz.g1, fz.b1, M, D, D, y_bf16=xl2, mean=mean1b, rstd=rstd1b)
+    qkv2 = _empty((M, 3 * D), BF16, dev)
+    ops.gemm(xl2, fz.Wqkv, ops.EPI_BF16, qkv2, bias=fz.bqkv)
+    del xl2
+    ao = _empty((M, D), BF16, dev)
+    lse = _empty((BT, H, P), F32, dev)
+    ops.attn_fwd(qkv2, ao, lse, BT, P, H)
+    sa = adp["S_Adapter"]
+    xb = _empty((M, D), BF16, dev)
+    ops.cast_bf16(x1, xb)
+    s_pre, s_h = _empty((M, r), BF16, dev), _empty((M, r), BF16, dev)
+    ops.gemm(xb, sa.W1, ops.EPI_ACT, s_h, bias=sa.b1, out2=s_pre, act=ops.ACT_GELU, af=f2, ntok=P, aux_grad=_AUX_GRAD)
+    xa = _empty((M, D), F32, dev)
+    ops.gemm(ao, fz.Wo, ops.EPI_F32, xa, bias=fz.bo, resid=x1)
+    x2 = _empty((M, D), F32, dev)
+    ops.gemm(s_h, sa.W2, ops.EPI_F32, x2, resid=xa, vec=f2.reshape(-1, 1) * sa.b2.reshape(1, -1), ldv=D, ntok=P)
+    del xa
+    # ---- 6: joint adaptation
+    x3, xn, mean2, rstd2, hcat_pre, a_s = _mlp_adapter_forward(x2, fz, tokm, P, save, af=f3)
+    if not save:
+        return x3, None
+    c = dict(x=x, mean1=mean1, rstd1=rstd1, qkv=qkv, at=at_, lse_w=lse_w, probs=probs, ta=ta, t_pre=t_pre, t_hs=t_hs, x1=x1,
+             mean1b=mean1b, rstd1b=rstd1b, qkv2=qkv2, ao=ao, lse=lse, xb=xb, s_pre=s_pre, s_h=s_h, x2=x2, mean2=mean2,
+             rstd2=rstd2, xn=xn, hcat_pre=hcat_pre, a_s=a_s, f1=f1, f2=f2, f3=f3, tokm=tokm)
+    return x3, c
+
+
+def _block_backward(dyb, c, fz: _Frozen, adp: Dict[str, _AdapterW], grads, B, T, N, P, H, window, keep: Optional[list]):
+    """dyb = d(loss)/d(x3) [M, D] bf16 with a zero slot row in every frame -> d(loss)/d(x) with the same property; the
+    adapters' gradients are accumulated into ``grads``."""
+    dev = dyb.device
+    M, D = dyb.shape
+    BT, r = B * T, fz.r
+    prompt = P != N
+    xv = lambda t: t.view(BT, P, -1)
+    fork = _Fork(dev, "bwd")
+    f1, f2, f3 = c["f1"], c["f2"], c["f3"]
+    dx2b, later = _mlp_adapter_backward(dyb, c["x2"], c["mean2"], c["rstd2"], c["xn"], c["hcat_pre"], c["a_s"], c["tokm"], fz,
+                                        grads["MLP_Adapter"], P, af=f3)
+    # ---- 5: x2 = x' + ao Wo^T + bo + s_h W2^T + f2 b2,  s_h = f2 GELU(xb W1^T + b1)
+    sa, gs = adp["S_Adapter"], grads["S_Adapter"]
+    s_h, xb = c["s_h"], c["xb"]
+    later.append(lambda: (ops.wgrad(dx2b, s_h, gs["D_fc2.weight"]), ops.colsum(dx2b, gs["D_fc2.bias"], af=f2, ntok=P)))
+    dpre = _empty((M, r), BF16, dev)
+    ops.gemm(dx2b, sa.W2T, ops.EPI_DACT, dpre, aux=c["s_pre"], act=ops.ACT_GELU, af=f2, ntok=P, aux_grad=_AUX_GRAD)
+    later.append(lambda: ops.wgrad(dpre, xb, gs["D_fc1.weight"], gs["D_fc1.bias"]))
+    dxs = _empty((M, D), BF16, dev)
+    ops.gemm(dpre, sa.W1T, ops.EPI_BF16, dxs)
+    dres = _empty((M, D), BF16, dev)
+    ops.add_bf16(dx2b, dxs, dres)
+    del dxs
+    dao = _empty((M, D), BF16, dev)
+    ops.gemm(dx2b, fz.WoT, ops.EPI_BF16, dao, reserve_cus=_DP_RESERVE)
+    dqkv = _empty((M, 3 * D), BF16, dev)
+    delta = _empty((BT, H, P), F32, dev)
+    ops.attn_bwd(c["qkv2"], c["ao"], dao, c["lse"], delta, dqkv, BT, P, H)
+    del dao
+    dxl = _empty((M, D), BF16, dev)
+    ops.gemm(dqkv, fz.WqkvT, ops.EPI_BF16, dxl, reserve_cus=_DP_RESERVE)
+    dx1b = _empty((M, D), BF16, dev)
+    ops.layernorm_bwd(dxl, c["x1"], fz.g1, c["mean1b"], c["rstd1b"], M, D, lddy=D, ldx=D, lddx=D, dres=dres, dx_bf16=dx1b)
+    del dres
+    dprompt = None
+    if prompt:          # the slot's row IS d(prompt) = one more gradient of ta's class rows; nothing else flows through the slot
+        dprompt = xv(dx1b)[:, N].to(F32, copy=True).contiguous()
+        xv(dx1b)[:, N] = 0
+    # ---- 4: x1 = x + t_hs W2^T + f1 b2,  t_hs = f1 GELU(ta W1^T + b1),  ta = [cls_attn | windows_attn] Wo^T + bo
+    tad, gt = adp["T_Adapter"], grads["T_Adapter"]
+    t_hs, ta = c["t_hs"], c["ta"]
+    later.append(lambda: (ops.wgrad(dx1b, t_hs, gt["D_fc2.weight"]), ops.colsum(dx1b, gt["D_fc2.bias"], af=f1, ntok=P)))
+    dtp = _empty((M, r), BF16, dev)
+    ops.gemm(dx1b, tad.W2T, ops.EPI_DACT, dtp, aux=c["t_pre"], act=ops.ACT_GELU, af=f1, ntok=P, aux_grad=_AUX_GRAD)
+    dta = _empty((M, D), BF16, dev)
+    ops.gemm(dtp, tad.W1T, ops.EPI_BF16, dta)
+    if prompt:
+        ops.add_rows(dta, P * D, dprompt)             # class rows: row 0 of every frame
+    dat = _empty((M, D), BF16, dev)
+    ops.gemm(dta, fz.WoT, ops.EPI_BF16, dat, reserve_cus=_DP_RESERVE)
+    del dta
+    # ---- 2, 3: the two attentions write disjoint rows of d(qkv): the window kernel the patch rows, cls_attn_bwd ADDS into
+    # the class rows (zeroed first, with the slot's)
+    xv(dqkv)[:, 0] = 0
+    if prompt:
+        xv(dqkv)[:, N] = 0
+    ops.win_attn_bwd(c["qkv"], c["at"], dat, c["lse_w"], delta, dqkv, B, T, N, H, window, P=P)
+    ops.cls_attn_bwd(c["qkv"], c["probs"], xv(dat)[:, 0].contiguous(), dqkv, B, T, P, H)
+    del dat
+    later.append(lambda: ops.wgrad(dtp, ta, gt["D_fc1.weight"], gt["D_fc1.bias"]))
+    ops.gemm(dqkv, fz.WqkvT, ops.EPI_BF16, dxl, reserve_cus=_DP_RESERVE)
+    del dqkv
+    dxb = _empty((M, D), BF16, dev)
+    ops.layernorm_bwd(dxl, c["x"], fz.g1, c["mean1"], c["rstd1"], M, D, lddy=D, ldx=D, lddx=D, dres=dx1b, dx_bf16=dxb)
+    if prompt:
+        xv(dxb)[:, N] = 0
+    _wgrads_beside(fork, later, keep)
+    return dxb
+
+
+class _FlashWinFn(torch.autograd.Function):
+    """imgs -> [B, D, T] features.  Differentiable inputs: ``AIM_FLASH_WIN._trainable_list()``."""
+
+    @staticmethod
+    def forward(ctx, model: "AIM_FLASH_WIN", grad_enabled: bool, imgs: torch.Tensor, *params: torch.Tensor):
+        L, H = model.layers, model.heads
+        B, C, T, Hh, Ww = imgs.shape
+        D, p = model.width, model.patch_size
+        G = Hh // p
+        N = G * G + 1
+        P = N + int(model.prompt)
+        BT = B * T
+        dev = imgs.device
+        temporal, lnp_w, lnp_b = params[0], params[1], params[2]
+        need_grad = grad_enabled and any(ctx.needs_input_grad)
+        frozen = model._frozen_operands()
+        staged = model._stage_adapters(frozen, params)
+        adp = []
+        for i in range(L):
+            fzi = frozen["blocks"][i]
+            k = 3 + i * 12
+            fzi.stage_mlp_bias(params[k + 1], params[k + 3], copy_b1=not staged)
+            adp.append({a: _AdapterW(*params[k + 4 * j:k + 4 * j + 4], bufs=fzi.small[a])
+                        for j, a in enumerate(_ADAPTERS) if a != "MLP_Adapter"})
+        Kp = frozen["conv"].shape[1]
+        A = _empty((BT * G * G, Kp), BF16, dev)
+        blend, model._blend_now = model._blend_now, None
+        if blend is not None:
+            ops.patchify_blend(imgs, A, B, T, Hh, Ww, p, Kp, *model._norm_now, blend=blend)
+        else:
+            ops.patchify(imgs, A, B, T, Hh, Ww, p, Kp, *model._norm_now)
+        tok = _empty((BT * G * G, D), BF16, dev)
+        ops.gemm(A, frozen["conv"], ops.EPI_BF16, tok)
+        del A
+        x0 = _empty((BT * N, D), F32, dev)
+        mean0, rstd0 = _empty((BT * N,), F32, dev), _empty((BT * N,), F32, dev)
+        tmp = temporal.detach().reshape(T, D).float().contiguous()
+        ops.embed_ln(tok, frozen["cls"], frozen["pos"], tmp, frozen["gpre"], frozen["bpre"], x0, mean0, rstd0, B, T, N, D)
+        if P != N:          # once per forward: into the P-row layout (row N = the prompt's slot, zero until block 0 fills it)
+            x = _empty((BT * P, D), F32, dev)
+            x.view(BT, P, D)[:, :N] = x0.view(BT, N, D)
+            x.view(BT, P, D)[:, N] = 0
+        else:
+            x = x0
+        del x0
+        if model.inference_precision == 'fp8' and not need_grad and not model._fp8_warned:
+            model._fp8_warned = True
+            _LOG.warning("fp8 inference was requested but AIM_FLASH_WIN has no fp8 path: this forward runs bf16")
+        fac = model._drop_masks_w(BT, model.training, dev)            # [L, 3, BT]
+        tokm = torch.ones(P, dtype=F32, device=dev)
+        if P != N:
+            tokm[N] = 0
+        window = clip_window(model.window_size, T, G)
+        ctxs: List[Optional[dict]] = []
+        for i in range(L):
+            x, c = _block_forward(x, frozen["blocks"][i], adp[i], B, T, N, P, H, window, fac[i, 0], fac[i, 1], fac[i, 2], tokm,
+                                  need_grad)
+            ctxs.append(c)
+        gw, gb = lnp_w.detach().float().contiguous(), lnp_b.detach().float().contiguous()
+        y = _empty((BT, D), F32, dev)
+        meanp, rstdp = _empty((BT,), F32, dev), _empty((BT,), F32, dev)
+        ops.layernorm_fwd(x, gw, gb, BT, D, P * D, y_f32=y, mean=meanp, rstd=rstdp)
+        if need_grad:
+            ctx.model, ctx.dims = model, (B, T, N, P, H, D, L)
+            ctx.saved = dict(ctxs=ctxs, adp=adp, tok=tok, mean0=mean0, rstd0=rstd0, tmp=tmp, xL=x, gw=gw, meanp=meanp,
+                             rstdp=rstdp, params=params, window=window)
+        return y.reshape(B, T, D).permute(0, 2, 1)      # '(b t) d -> b d t'
+
+    @staticmethod
+    def backward(ctx, dout):
+        model = ctx.model
+        B, T, N, P, H, D, L = ctx.dims
+        s = ctx.saved
+        BT = B * T
+        dev = dout.device
+        frozen = model._frozen_operands()
+        params = s["params"]
+        grads_out: List[Optional[torch.Tensor]] = [None] * len(params)
+        in_place = [False] * len(params)
+
+        def buf(k):      # fp32, every kernel ACCUMULATES: straight into param.grad under dist.build_optimizer (grad_in_place)
+            p_ = params[k]
+            if (model.grad_in_place and p_.requires_grad and p_.grad is not None and p_.grad.dtype == F32
+                    and p_.grad.is_contiguous() and p_.grad.device == dev):
+                in_place[k] = True
+                return p_.grad
+            return torch.zeros_like(p_, dtype=F32)
+
+        layer_grads = []
+        for i in range(L):
+            lg = {}
+            for j, a in enumerate(_ADAPTERS):
+                k = 3 + i * 12 + j * 4
+                lg[a] = {}
+                for e, leaf in enumerate(_ADAPTER_LEAVES):
+                    lg[a][leaf] = grads_out[k + e] = buf(k + e)
+            layer_grads.append(lg)
+        dgw, dgb = buf(1), buf(2)
+        dy = dout.permute(0, 2, 1).reshape(BT, D).contiguous().float()
+        dxb = torch.zeros((BT * P, D), dtype=BF16, device=dev)          # ln_post touches the class rows only
+        ops.layernorm_bwd(dy, s["xL"], s["gw"], s["meanp"], s["rstdp"], BT, D, lddy=D, ldx=P * D, lddx=P * D,
+                          dx_bf16=dxb, dgamma=dgw, dbeta=dgb)
+        keep: list = []
+        hook = model.grad_ready_hook
+        for i in reversed(range(L)):
+            dxb = _block_backward(dxb, s["ctxs"][i], frozen["blocks"][i], s["adp"][i], layer_grads[i], B, T, N, P, H,
+                                  s["window"], keep)
+            s["ctxs"][i] = None
+            if hook is not None:
+                k0 = 3 + i * 12
+                hook(i, all(in_place[k0:k0 + 12]), _Fork.streams(dev))
+        if P != N:          # once per backward: back to the embedding's N tokens per frame (the slot's row is zero)
+            dxb = dxb.view(BT, P, D)[:, :N].contiguous().view(BT * N, D)
+        dtmp = buf(0)
+        ops.embed_bwd(dxb, s["tok"], frozen["cls"], frozen["pos"], s["tmp"], frozen["gpre"], s["mean0"], s["rstd0"],
+                      dtmp.view(T, D), B, T, N, D)
+        grads_out[0] = dtmp.view(1, T, D)
+        grads_out[1], grads_out[2] = dgw, dgb
+        _Fork.join_detached(dev)       # every weight gradient is in place before autograd hands them on
+        keep.clear()
+        for k, p_ in enumerate(params):
+            if not p_.requires_grad or in_place[k]:
+                grads_out[k] = None
+            elif grads_out[k] is not None and grads_out[k].dtype != p_.dtype:
+                grads_out[k] = grads_out[k].to(p_.dtype)
+        ctx.saved = None
+        return (None, None, None) + tuple(grads_out)
+
+
+@BACKBONES.register_module()
+class AIM_FLASH_WIN(ViT_CLIP):
+    """AIM with 3-D window temporal attention and a temporal class-token prompt (reference vitclip_aim_flash_win.py:276-433)."""
+
+    def __init__(self, input_resolution: int, num_frames: int, patch_size: int, width: int, layers: int, heads: int,
+                 drop_path_rate, num_tadapter=1, adapter_scale=0.5, pretrained=None, checkpoint=False, use_flash_attn=True,
+                 prompt=True, wind_attn=False, window_size=(32, 2, 2), not_shift=True):
+        if not wind_attn:
+            raise NotImplementedError("AIM_FLASH_WIN(wind_attn=False) (vitclip_aim_flash_win.py:147-156: temporal attention "
+                                      "over the frames of every token) is the stock AIM block: build type='AIM' for it")
+        if not not_shift:
+            raise NotImplementedError("AIM_FLASH_WIN(not_shift=False): the reference's shifted branch rolls the windows back and "
+                                      "then discards the result (vitclip_aim_flash_win.py:188 against :192), so its output is "
+                                      "mis-aligned by the shift; it is not built")
+        if num_tadapter != 1:
+            raise NotImplementedError("AIM_FLASH_WIN(num_tadapter=2) (T_Adapter_in) is not built")
+        if checkpoint:
+            raise NotImplementedError("AIM_FLASH_WIN(checkpoint=True) (activation recompute per block) is not built")
+        G = input_resolution // patch_size
+        win = clip_window(window_size, num_frames, G)
+        if len(tuple(window_size)) != 3 or any(w <= 0 for w in win) or num_frames % win[0] or G % win[1] or G % win[2]:
+            raise ValueError(f"window_size={tuple(window_size)} (clipped to {win}) does not divide the {num_frames} x {G} x {G} grid")
+        if win[0] * win[1] * win[2] > ops.WIN_ATTN_MAX_S:
+            raise ValueError(f"{win[0] * win[1] * win[2]} tokens per window: the window attention kernels take at most "
+                             f"{ops.WIN_ATTN_MAX_S}")
+        super().__init__(input_resolution, num_frames, patch_size, width, 0, heads, drop_path_rate,
+                         adapter_scale=adapter_scale, pretrained=pretrained)
+        self.layers = layers
+        self.transformer = WinTransformer(num_frames, width, layers, heads, adapter_scale, drop_path_rate)
+        self.num_tadapter, self.use_flash_attn, self.prompt = num_tadapter, use_flash_attn, bool(prompt)
+        self.wind_attn, self.window_size, self.not_shift = wind_attn, tuple(int(w) for w in window_size), not_shift
+        self.variant = 'aim_flash_win'
+        self._fp8_warned = False
+
+    def set_precision(self, precision: str):
+        if precision == 'fp32':
+            raise NotImplementedError("AIM_FLASH_WIN has no fp32 verification mode")
+        return super().set_precision(precision)
+
+    def init_weights(self, pretrained=None):
+        """Reference ``init_weights`` (:300-398): CLIP's ``in_proj_*`` / ``c_fc`` / ``c_proj`` go into ``Wqkv`` / ``fc1`` / ``fc2``."""
+        if pretrained:
+            self.pretrained = pretrained
+        if isinstance(self.pretrained, str):
+            try:
+                import clip  # noqa: F401
+            except ImportError as e:
+                raise RuntimeError("pretrained=%r needs the OpenAI `clip` package and its downloaded weights; load a state_dict "
+                                   "with this class's names instead" % (self.pretrained,)) from e
+            name, self.pretrained = self.pretrained, None
+            super().init_weights()
+            self.pretrained = name
+            clip_model, _ = clip.load("ViT-B/16" if self.layers == 12 else "ViT-L/14", device="cpu")
+            sd = clip_model.visual.state_dict()
+            del clip_model
+            del sd['proj']
+            swaps = (('attn.in_proj_weight', 'attn.Wqkv.weight'), ('attn.in_proj_bias', 'attn.Wqkv.bias'),
+                     ('mlp.c_fc.', 'mlp.fc1.'), ('mlp.c_proj.', 'mlp.fc2.'))
+            out = {}
+            for k, v in sd.items():
+                for a, b in swaps:
+                    k = k.replace(a, b)
+                out[k] = v
+            msg = self.load_state_dict(out, strict=False)
+            _LOG.info('Missing keys: %s', msg.missing_keys)
+            _LOG.info('Unexpected keys: %s', msg.unexpected_keys)
+            self._frozen_cache = None
+        else:
+            super().init_weights()
+
+    def _frozen_operands(self):
+        """bf16 copies of the frozen weights; rebuilt only when a frozen tensor changed or moved."""
+        key = tuple((p.data_ptr(), p._version) for p in self._frozen_params())
+        if self._frozen_cache is not None and self._frozen_cache[0] == key:
+            return self._frozen_cache[1]
+        D, p = self.width, self.patch_size
+        K = 3 * p * p
+        Kp = (K + 63) // 64 * 64
+        dev = self.conv1.weight.device
+        wc = torch.zeros((D, Kp), dtype=F32, device=dev)
+        wc[:, :K] = self.conv1.weight.detach().reshape(D, K).float()
+        conv = torch.empty((D, Kp), dtype=BF16, device=dev)
+        ops.cast_bf16(wc, conv)
+        f = lambda t: t.detach().float().contiguous()
+        out = dict(conv=conv, cls=f(self.class_embedding), pos=f(self.positional_embedding), gpre=f(self.ln_pre.weight),
+                   bpre=f(self.ln_pre.bias), blocks=[_Frozen(_frozen_view(b)) for b in self.transformer.resblocks])
+        self._frozen_cache = (key, out)
+        return out
+
+    def _drop_masks_w(self, BT, training, dev):
+        """The three DropPath factors of every block per FRAME, ``[L, 3, BT]``, in the reference's draw order (:200, :215,
+        :224); the second and third carry the adapter scale, the first does not."""
+        blocks = self.transformer.resblocks
+        L = len(blocks)
+        key = (str(dev), tuple(float(b.drop_prob) for b in blocks), tuple(float(b.scale) for b in blocks))
+        cached = getattr(self, "_drop_consts_w", None)
+        if cached is None or cached[0] != key:
+            rates, scale = torch.tensor(key[1], dtype=F32).view(L, 1, 1), torch.tensor(key[2], dtype=F32).view(L, 1, 1)
+            scale3 = torch.cat([torch.ones_like(scale), scale, scale], dim=1)            # [L, 3, 1]
+            keep = 1.0 - rates
+            fac = torch.where(keep > 0, scale3 / keep.clamp_min(1e-12), torch.zeros_like(scale3))
+            cached = (key, float(rates.max()), scale3.to(dev), keep.to(dev), fac.to(dev))
+            self._drop_consts_w = cached
+        _, max_rate, scale_d, keep_d, fac_d = cached
+        if not training or max_rate <= 0.:
+            return scale_d.expand(L, 3, BT).contiguous()
+        u = torch.rand((L, 3, BT), dtype=F32, device=dev)
+        return ((u < keep_d).to(F32) * fac_d).contiguous()
+
+    def forward(self, x: torch.Tensor):
+        blend, self._blend_next = self._blend_next, None
+        if not x.is_cuda:
+            raise RuntimeError("aim_amd.AIM_FLASH_WIN runs on MI355X only (HIP kernels); there is no CPU fallback")
+        B, C, T, H, W = x.shape
+        if T != self.num_frames:
+            raise ValueError(f"expected {self.num_frames} frames, got {T}")
+        if C != 3 or H != self.input_resolution or W != self.input_resolution:
+            raise ValueError(f"expected input [B,3,{T},{self.input_resolution},{self.input_resolution}], got {tuple(x.shape)}")
+        N = (H // self.patch_size) ** 2 + 1
+        if N + int(self.prompt) > 288:
+            raise ValueError(f"{N + int(self.prompt)} tokens per frame: the spatial attention kernels take at most 288")
+        if T > 32:
+            raise ValueError(f"{T} frames: the class-token attention kernels take at most 32")
+        if x.dtype == torch.float16:
+            x = x.float()
+        x = x.contiguous()
+        self._norm_now = (self._norm_mean, self._norm_std) if x.dtype == torch.uint8 else (None, None)
+        self._norm_mean = self._norm_std = None
+        if x.dtype == torch.uint8 and self._norm_now[0] is None:
+            raise TypeError("uint8 clips need a GPUNormalize module hook on the backbone (module_hooks.py:35-87)")
+        if blend is not None and (x.dtype not in (torch.float32, torch.uint8) or blend.partner.numel() != B):
+            raise TypeError(f"a fused blending needs float32 or uint8 clips and one partner per clip, got {x.dtype} and "
+                            f"{blend.partner.numel()} partners for {B} clips")
+        self._blend_now = blend
+        y = _FlashWinFn.apply(self, torch.is_grad_enabled(), x, *self._trainable_list())     # [B, D, T]
+        return y.unsqueeze(-1).unsqueeze(-1)

@@ -635,11 +635,12 @@ def _block_forward(x, fz: _Frozen, adp: Dict[str, _AdapterW], B, T, N, H, dms1, 
     return x2, ctx
 
 
-def _mlp_adapter_forward(x1, fz: _Frozen, dms2, N, save: bool, small_tile: bool = False):
+def _mlp_adapter_forward(x1, fz: _Frozen, dms2, N, save: bool, small_tile: bool = False, af=None):
     """Joint adaptation (vit_clip.py:285-286; identical in vitclip_aim.py:209-210): x2 = x1 + mlp(ln_2(x1)) +
     drop_path(scale * MLP_Adapter(ln_2(x1))).  One GEMM for [c_fc | D_fc1] (N = 4D + r; QuickGELU on the MLP columns,
     dms2 * GELU on the adapter's) and one for [c_proj | D_fc2] (K = 4D + r); the adapter's token-scaled bias rides along
-    as `vec`.  Returns (x2, xn, mean2, rstd2, hcat_pre, a_s)."""
+    as `vec`.  ``af`` [M / N]: one more factor per FRAME on the adapter's term (a DropPath over frames,
+    vitclip_aim_flash_win.py:224); the factor of row m is af[m / N] * dms2[m % N].  Returns (x2, xn, mean2, rstd2, hcat_pre, a_s)."""
     dev = x1.device
     M, D = x1.shape
     r, H4 = fz.r, 4 * D
@@ -655,10 +656,14 @@ def _mlp_adapter_forward(x1, fz: _Frozen, dms2, N, save: bool, small_tile: bool 
         hcat_pre = _empty((M, H4 + r), BF16, dev) if (save or M < 1024 or small_tile) else None     # (the small-M kernels always store it)
     hcat = _empty((M, H4 + r), BF16, dev)
     ops.gemm(xn, fz.Wcat1, ops.EPI_ACT, hcat, bias=fz.bcat1, out2=hcat_pre, act=ops.ACT_QGELU, n_split=H4,
-             act2=ops.ACT_GELU, at=dms2, ntok=N, aux_grad=_AUX_GRAD, aux_frag=frag and hcat_pre is not None,
+             act2=ops.ACT_GELU, af=af, at=dms2, ntok=N, aux_grad=_AUX_GRAD, aux_frag=frag and hcat_pre is not None,
              small_tile=small_tile)
     x2 = _empty((M, D), F32, dev)
-    ops.gemm(hcat, fz.Wcat2, ops.EPI_F32, x2, bias=fz.bpr, resid=x1, vec=fz.b2row, ldv=0, bt=dms2, ntok=N, small_tile=small_tile)
+    if af is None:
+        vec, ldv = fz.b2row, 0
+    else:                               # the adapter's bias under the frame factor: one row per frame
+        vec, ldv = af.reshape(-1, 1) * fz.b2row, D
+    ops.gemm(hcat, fz.Wcat2, ops.EPI_F32, x2, bias=fz.bpr, resid=x1, vec=vec, ldv=ldv, bt=dms2, ntok=N, small_tile=small_tile)
     # the adapter's activation slice stays a VIEW of hcat (wgrad takes a row stride): no copy kernel in the forward, at the
     # price of keeping hcat (M x (4D + r) bf16) alive until this block's backward
     a_s = hcat[:, H4:] if save else None
@@ -666,7 +671,7 @@ def _mlp_adapter_forward(x1, fz: _Frozen, dms2, N, save: bool, small_tile: bool 
 
 
 def _mlp_adapter_backward(dyb, x_in, mean2, rstd2, xn, hcat_pre, a_s, dms2, fz: _Frozen, gm, N, fsum=None,
-                          small_tile: bool = False):
+                          small_tile: bool = False, af=None):
     """Backward of ``_mlp_adapter_forward``: returns (d(x_in) as bf16, the weight-gradient closures).  x2 = x_in +
     [h | a_s] [W_proj | W2]^T + b_proj + dms2[tok] * b2.  ``fsum = (w [N], partial [frames, LN_FSUM_GROUPS, D])``: the ln_2
     backward also leaves the per-frame sums of w[n] * d(x_in) (in token groups) in ``partial``."""
@@ -675,13 +680,16 @@ def _mlp_adapter_backward(dyb, x_in, mean2, rstd2, xn, hcat_pre, a_s, dms2, fz: 
     r, H4 = fz.r, 4 * D
     big_later: list = []
     # D_fc2: weight gradient + the DropPath-scaled bias gradient in one pass over dyb
-    if _DETACH_BIG:
+    if af is not None:                  # a frame factor as well: the bias gradient is a column sum of its own
+        big_later.append(lambda: (ops.wgrad(dyb, a_s, gm["D_fc2.weight"]),
+                                  ops.colsum(dyb, gm["D_fc2.bias"], af=af, at=dms2, ntok=N)))
+    elif _DETACH_BIG:
         big_later.append(lambda: ops.wgrad(dyb, a_s, gm["D_fc2.weight"], gm["D_fc2.bias"], at=dms2, ntok=N))
     else:
         ops.wgrad(dyb, a_s, gm["D_fc2.weight"], gm["D_fc2.bias"], at=dms2, ntok=N)
     dcat = _empty((M, H4 + r), BF16, dev)           # [dh_pre | da_pre]
     ops.gemm(dyb, fz.WcatT2, ops.EPI_DACT, dcat, aux=hcat_pre, act=ops.ACT_QGELU, n_split=H4, act2=ops.ACT_GELU,
-             at=dms2, ntok=N, aux_grad=_AUX_GRAD, aux_frag=_AUX_FRAG and dyb.shape[0] >= 1024 and not small_tile,
+             af=af, at=dms2, ntok=N, aux_grad=_AUX_GRAD, aux_frag=_AUX_FRAG and dyb.shape[0] >= 1024 and not small_tile,
              reserve_cus=_DP_RESERVE, small_tile=small_tile)
     if _DETACH_BIG:
         big_later.append(lambda: ops.wgrad(dcat[:, H4:], xn, gm["D_fc1.weight"], gm["D_fc1.bias"]))

@@ -326,6 +326,30 @@ def attn_bwd_shift(qkv, out, dout, lse, delta, dqkv, B, T, N, H, shifts):
                                             _shift_table(shifts, H), _stream()), "aim_attn_bwd_shift")
 
 
+WIN_ATTN_MAX_S = 4096   # AIM_WIN_ATTN_MAX_S of include/aim_kernels.h (ABI 11)
+
+
+def win_attn_fwd(qkv, out, lse, B, T, N, H, window, P=None):
+    """Attention inside the (wt, wh, ww) windows of the patch grid of B clips of T frames (class rows untouched); the
+    partition is addressing inside the kernel.  P (default N): token rows per frame of the buffers, the rows behind a
+    frame's N tokens are untouched too.  out [B*T*P, D], lse [B*T, H, P]."""
+    _chk(qkv, BF16, "qkv"); _chk(out, BF16, "out"); _chk(lse, F32, "lse")
+    wt, wh, ww = (int(w) for w in window)
+    check(load_library().aim_win_attn_fwd(qkv.data_ptr(), out.data_ptr(), lse.data_ptr(), B, T, N, N if P is None else P, H, wt, wh, ww,
+                                          _stream()),
+          "aim_win_attn_fwd")
+
+
+def win_attn_bwd(qkv, out, dout, lse, delta, dqkv, B, T, N, H, window, P=None):
+    """backward of win_attn_fwd: writes the patch rows of dqkv [B*T*P, 3D] and of delta [B*T, H, P]."""
+    _chk(qkv, BF16, "qkv"); _chk(out, BF16, "out"); _chk(dout, BF16, "dout"); _chk(dqkv, BF16, "dqkv")
+    _chk(lse, F32, "lse"); _chk(delta, F32, "delta")
+    wt, wh, ww = (int(w) for w in window)
+    check(load_library().aim_win_attn_bwd(qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(), delta.data_ptr(),
+                                          dqkv.data_ptr(), B, T, N, N if P is None else P, H, wt, wh, ww, _stream()),
+          "aim_win_attn_bwd")
+
+
 def attn_fwd_cls(qkv, out_cls, lse_cls, BT, N, H):
     """attn_fwd for the class query of every (frame, head) alone: out_cls [BT, D], lse_cls [BT, H]."""
     _chk(qkv, BF16, "qkv"); _chk(out_cls, BF16, "out_cls"); _chk(lse_cls, F32, "lse_cls")

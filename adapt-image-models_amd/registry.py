@@ -139,6 +139,8 @@ def register_into_mmaction() -> bool:
     from .backbone import ViT_CLIP
     MB.register_module(name="ViT_CLIP", force=True, module=ViT_CLIP)
     MB.register_module(name="AIM", force=True, module=AIM)       # stock AIM (vitclip_aim.py:353), wind_attn=False
+    from .aim_flash_win import AIM_FLASH_WIN
+    MB.register_module(name="AIM_FLASH_WIN", force=True, module=AIM_FLASH_WIN)     # vitclip_aim_flash_win.py:276, wind_attn=True
     return True
 
 

@@ -32,7 +32,7 @@ extern "C" {
 
 typedef uint16_t aim_bf16;
 
-#define AIM_ABI_VERSION 10
+#define AIM_ABI_VERSION 11
 
 int aim_version(void);                /* == AIM_ABI_VERSION */
 const char* aim_last_error(void);     /* message of the last failing call on this thread */
@@ -224,6 +224,29 @@ int aim_attn_fwd_shift(const aim_bf16* qkv, aim_bf16* out, float* lse, int BT, i
 int aim_attn_bwd_shift(const aim_bf16* qkv, const aim_bf16* out, const aim_bf16* dout, const float* lse,
                        float* delta /* scratch [BT, H, N] f32 */, aim_bf16* dqkv, int BT, int N, int H, int B, int T,
                        const int* shifts, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Self-attention inside 3-D windows of the patch grid (ABI 11; AIM_FLASH_WIN's temporal branch,
+ * vitclip_aim_flash_win.py:146-225: window_partition, attention, window_reverse on the patch tokens).
+ *   B clips of T frames of N = G*G + 1 tokens, stored P >= N token rows per frame (P > N: spare rows behind a frame's
+ *   tokens, e.g. the slot of a prompt token; never touched).  A window of (wt, wh, ww) holds the S = wt*wh*ww patch
+ *   tokens (dt, dh, dw) whose row is (b*T + it*wt + dt)*P + 1 + (ih*wh + dh)*G + iw*ww + dw.  The gather and its inverse are
+ *   addresses inside the kernels: no window-partitioned copy of anything exists.  An extent that reaches the grid's is
+ *   clipped to it (the reference's get_window_size); the clipped extents must divide (T, G, G).
+ *   qkv [B*T*P, 3*D] bf16 (q | k | v, D = H*64) ; out, dout [B*T*P, D] bf16 ; dqkv [B*T*P, 3*D] bf16 ;
+ *   lse, delta [B*T, H, P] f32 (delta = dout . out per row and head: written by bwd, scratch for the caller).
+ *   The class row (token 0) and the spare rows of every frame are never read, and never written in out, lse, delta, dqkv.
+ * Streaming softmax: K and V pass through LDS in 64-key tiles under an online (max, sum) rescale, so S is bounded only by
+ * AIM_WIN_ATTN_MAX_S; more, a non-square N - 1 or extents that do not divide are refused before any launch.
+ * bwd recomputes the probabilities from lse in two kernels (delta + dQ with the queries resident, then dK + dV with the
+ * keys resident): one writer per row, fixed summation order, no atomics, the same bits on every run.  Nothing is summed
+ * across workgroups, so bwd takes no workspace; `delta` is its only scratch.
+ * ------------------------------------------------------------------------------------------ */
+#define AIM_WIN_ATTN_MAX_S 4096
+int aim_win_attn_fwd(const aim_bf16* qkv, aim_bf16* out, float* lse, int B, int T, int N, int P, int H, int wt, int wh,
+                     int ww, void* stream);
+int aim_win_attn_bwd(const aim_bf16* qkv, const aim_bf16* out, const aim_bf16* dout, const float* lse, float* delta,
+                     aim_bf16* dqkv, int B, int T, int N, int P, int H, int wt, int wh, int ww, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Temporal attention over the T class tokens of each clip -- vit_clip.py:220-224 with
