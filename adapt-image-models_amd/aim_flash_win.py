@@ -40,10 +40,10 @@ import torch
 from torch import nn
 
 from . import ops
-from .backbone import (_ADAPTER_LEAVES, _ADAPTERS, _AUX_GRAD, _DP_RESERVE, BF16, F32, Adapter, LayerNorm, QuickGELU, ViT_CLIP,
-                       _AdapterW, _empty, _Fork, _Frozen, _mlp_adapter_backward, _mlp_adapter_forward)
+from .backbone import (_AUX_GRAD, _DP_RESERVE, BF16, F32, Adapter, LayerNorm, QuickGELU, ViT_CLIP, _AdapterW, _embed_backward,
+                       _embed_forward, _empty, _Fork, _Frozen, _GradBufs, _ln_post_backward, _ln_post_forward,
+                       _mlp_adapter_backward, _mlp_adapter_forward, _wgrads_beside)
 from .registry import BACKBONES
-from .zeroi2v import _wgrads_beside
 
 _LOG = logging.getLogger("aim_amd")
 
@@ -257,28 +257,8 @@ class _FlashWinFn(torch.autograd.Function):
         temporal, lnp_w, lnp_b = params[0], params[1], params[2]
         need_grad = grad_enabled and any(ctx.needs_input_grad)
         frozen = model._frozen_operands()
-        staged = model._stage_adapters(frozen, params)
-        adp = []
-        for i in range(L):
-            fzi = frozen["blocks"][i]
-            k = 3 + i * 12
-            fzi.stage_mlp_bias(params[k + 1], params[k + 3], copy_b1=not staged)
-            adp.append({a: _AdapterW(*params[k + 4 * j:k + 4 * j + 4], bufs=fzi.small[a])
-                        for j, a in enumerate(_ADAPTERS) if a != "MLP_Adapter"})
-        Kp = frozen["conv"].shape[1]
-        A = _empty((BT * G * G, Kp), BF16, dev)
-        blend, model._blend_now = model._blend_now, None
-        if blend is not None:
-            ops.patchify_blend(imgs, A, B, T, Hh, Ww, p, Kp, *model._norm_now, blend=blend)
-        else:
-            ops.patchify(imgs, A, B, T, Hh, Ww, p, Kp, *model._norm_now)
-        tok = _empty((BT * G * G, D), BF16, dev)
-        ops.gemm(A, frozen["conv"], ops.EPI_BF16, tok)
-        del A
-        x0 = _empty((BT * N, D), F32, dev)
-        mean0, rstd0 = _empty((BT * N,), F32, dev), _empty((BT * N,), F32, dev)
-        tmp = temporal.detach().reshape(T, D).float().contiguous()
-        ops.embed_ln(tok, frozen["cls"], frozen["pos"], tmp, frozen["gpre"], frozen["bpre"], x0, mean0, rstd0, B, T, N, D)
+        adp = model._stage_adapters(frozen, params)
+        tok, x0, mean0, rstd0, tmp = _embed_forward(model, frozen, imgs, temporal)
         if P != N:          # once per forward: into the P-row layout (row N = the prompt's slot, zero until block 0 fills it)
             x = _empty((BT * P, D), F32, dev)
             x.view(BT, P, D)[:, :N] = x0.view(BT, N, D)
@@ -299,10 +279,7 @@ class _FlashWinFn(torch.autograd.Function):
             x, c = _block_forward(x, frozen["blocks"][i], adp[i], B, T, N, P, H, window, fac[i, 0], fac[i, 1], fac[i, 2], tokm,
                                   need_grad)
             ctxs.append(c)
-        gw, gb = lnp_w.detach().float().contiguous(), lnp_b.detach().float().contiguous()
-        y = _empty((BT, D), F32, dev)
-        meanp, rstdp = _empty((BT,), F32, dev), _empty((BT,), F32, dev)
-        ops.layernorm_fwd(x, gw, gb, BT, D, P * D, y_f32=y, mean=meanp, rstd=rstdp)
+        y, gw, meanp, rstdp = _ln_post_forward(x, lnp_w, lnp_b, BT, P)
         if need_grad:
             ctx.model, ctx.dims = model, (B, T, N, P, H, D, L)
             ctx.saved = dict(ctxs=ctxs, adp=adp, tok=tok, mean0=mean0, rstd0=rstd0, tmp=tmp, xL=x, gw=gw, meanp=meanp,
@@ -317,57 +294,22 @@ class _FlashWinFn(torch.autograd.Function):
         BT = B * T
         dev = dout.device
         frozen = model._frozen_operands()
-        params = s["params"]
-        grads_out: List[Optional[torch.Tensor]] = [None] * len(params)
-        in_place = [False] * len(params)
-
-        def buf(k):      # fp32, every kernel ACCUMULATES: straight into param.grad under dist.build_optimizer (grad_in_place)
-            p_ = params[k]
-            if (model.grad_in_place and p_.requires_grad and p_.grad is not None and p_.grad.dtype == F32
-                    and p_.grad.is_contiguous() and p_.grad.device == dev):
-                in_place[k] = True
-                return p_.grad
-            return torch.zeros_like(p_, dtype=F32)
-
-        layer_grads = []
-        for i in range(L):
-            lg = {}
-            for j, a in enumerate(_ADAPTERS):
-                k = 3 + i * 12 + j * 4
-                lg[a] = {}
-                for e, leaf in enumerate(_ADAPTER_LEAVES):
-                    lg[a][leaf] = grads_out[k + e] = buf(k + e)
-            layer_grads.append(lg)
-        dgw, dgb = buf(1), buf(2)
+        gbufs = _GradBufs(model, s["params"], dev)
+        layer_grads = gbufs.layers(L, model._adapter_names)
+        dgw, dgb = gbufs.buf(1), gbufs.buf(2)
         dy = dout.permute(0, 2, 1).reshape(BT, D).contiguous().float()
-        dxb = torch.zeros((BT * P, D), dtype=BF16, device=dev)          # ln_post touches the class rows only
-        ops.layernorm_bwd(dy, s["xL"], s["gw"], s["meanp"], s["rstdp"], BT, D, lddy=D, ldx=P * D, lddx=P * D,
-                          dx_bf16=dxb, dgamma=dgw, dbeta=dgb)
+        dxb = _ln_post_backward(dy, s, dgw, dgb, BT, P)
         keep: list = []
-        hook = model.grad_ready_hook
         for i in reversed(range(L)):
             dxb = _block_backward(dxb, s["ctxs"][i], frozen["blocks"][i], s["adp"][i], layer_grads[i], B, T, N, P, H,
                                   s["window"], keep)
             s["ctxs"][i] = None
-            if hook is not None:
-                k0 = 3 + i * 12
-                hook(i, all(in_place[k0:k0 + 12]), _Fork.streams(dev))
+            gbufs.layer_ready(i)
         if P != N:          # once per backward: back to the embedding's N tokens per frame (the slot's row is zero)
             dxb = dxb.view(BT, P, D)[:, :N].contiguous().view(BT * N, D)
-        dtmp = buf(0)
-        ops.embed_bwd(dxb, s["tok"], frozen["cls"], frozen["pos"], s["tmp"], frozen["gpre"], s["mean0"], s["rstd0"],
-                      dtmp.view(T, D), B, T, N, D)
-        grads_out[0] = dtmp.view(1, T, D)
-        grads_out[1], grads_out[2] = dgw, dgb
-        _Fork.join_detached(dev)       # every weight gradient is in place before autograd hands them on
-        keep.clear()
-        for k, p_ in enumerate(params):
-            if not p_.requires_grad or in_place[k]:
-                grads_out[k] = None
-            elif grads_out[k] is not None and grads_out[k].dtype != p_.dtype:
-                grads_out[k] = grads_out[k].to(p_.dtype)
+        grads = _embed_backward(gbufs, frozen, s, dxb, keep, B, T, N, D)
         ctx.saved = None
-        return (None, None, None) + tuple(grads_out)
+        return grads
 
 
 @BACKBONES.register_module()
@@ -440,24 +382,8 @@ class AIM_FLASH_WIN(ViT_CLIP):
         else:
             super().init_weights()
 
-    def _frozen_operands(self):
-        """bf16 copies of the frozen weights; rebuilt only when a frozen tensor changed or moved."""
-        key = tuple((p.data_ptr(), p._version) for p in self._frozen_params())
-        if self._frozen_cache is not None and self._frozen_cache[0] == key:
-            return self._frozen_cache[1]
-        D, p = self.width, self.patch_size
-        K = 3 * p * p
-        Kp = (K + 63) // 64 * 64
-        dev = self.conv1.weight.device
-        wc = torch.zeros((D, Kp), dtype=F32, device=dev)
-        wc[:, :K] = self.conv1.weight.detach().reshape(D, K).float()
-        conv = torch.empty((D, Kp), dtype=BF16, device=dev)
-        ops.cast_bf16(wc, conv)
-        f = lambda t: t.detach().float().contiguous()
-        out = dict(conv=conv, cls=f(self.class_embedding), pos=f(self.positional_embedding), gpre=f(self.ln_pre.weight),
-                   bpre=f(self.ln_pre.bias), blocks=[_Frozen(_frozen_view(b)) for b in self.transformer.resblocks])
-        self._frozen_cache = (key, out)
-        return out
+    def _frozen_block(self, blk):
+        return _Frozen(_frozen_view(blk))
 
     def _drop_masks_w(self, BT, training, dev):
         """The three DropPath factors of every block per FRAME, ``[L, 3, BT]``, in the reference's draw order (:200, :215,
@@ -480,29 +406,12 @@ class AIM_FLASH_WIN(ViT_CLIP):
         return ((u < keep_d).to(F32) * fac_d).contiguous()
 
     def forward(self, x: torch.Tensor):
-        blend, self._blend_next = self._blend_next, None
-        if not x.is_cuda:
-            raise RuntimeError("aim_amd.AIM_FLASH_WIN runs on MI355X only (HIP kernels); there is no CPU fallback")
-        B, C, T, H, W = x.shape
-        if T != self.num_frames:
-            raise ValueError(f"expected {self.num_frames} frames, got {T}")
-        if C != 3 or H != self.input_resolution or W != self.input_resolution:
-            raise ValueError(f"expected input [B,3,{T},{self.input_resolution},{self.input_resolution}], got {tuple(x.shape)}")
-        N = (H // self.patch_size) ** 2 + 1
+        blend = self._take_blend_check_clip(x, "AIM_FLASH_WIN")
+        T, N = x.shape[2], (x.shape[3] // self.patch_size) ** 2 + 1
         if N + int(self.prompt) > 288:
             raise ValueError(f"{N + int(self.prompt)} tokens per frame: the spatial attention kernels take at most 288")
         if T > 32:
             raise ValueError(f"{T} frames: the class-token attention kernels take at most 32")
-        if x.dtype == torch.float16:
-            x = x.float()
-        x = x.contiguous()
-        self._norm_now = (self._norm_mean, self._norm_std) if x.dtype == torch.uint8 else (None, None)
-        self._norm_mean = self._norm_std = None
-        if x.dtype == torch.uint8 and self._norm_now[0] is None:
-            raise TypeError("uint8 clips need a GPUNormalize module hook on the backbone (module_hooks.py:35-87)")
-        if blend is not None and (x.dtype not in (torch.float32, torch.uint8) or blend.partner.numel() != B):
-            raise TypeError(f"a fused blending needs float32 or uint8 clips and one partner per clip, got {x.dtype} and "
-                            f"{blend.partner.numel()} partners for {B} clips")
-        self._blend_now = blend
+        x = self._arm_clip(x, blend)
         y = _FlashWinFn.apply(self, torch.is_grad_enabled(), x, *self._trainable_list())     # [B, D, T]
         return y.unsqueeze(-1).unsqueeze(-1)

@@ -819,6 +819,146 @@ def _block_backward(dyb, c, fz: _Frozen, adp: Dict[str, _AdapterW], grads, B, T,
 
 
 # ----------------------------------------------------------------------------------------------
+# what the CLIP-family autograd functions share (this file, zeroi2v.py, aim_flash_win.py): plain functions called in place --
+# the stem, ln_post on P-row streams, the gradient buffers, the tail.  Each Function keeps its own forward / backward, its own
+# layout step and its own block loop.
+# ----------------------------------------------------------------------------------------------
+def _wgrads_beside(fork: _Fork, calls: list, keep: Optional[list]):
+    """The block's weight-gradient launches: on the detached stream behind everything the main stream has queued (nobody
+    downstream waits for them until ``_Fork.join_detached``), or inline when the streams are switched off."""
+    if not calls:
+        return
+    if fork.enabled and _DETACH_WGRAD and keep is not None:
+        fork.run_beside(lambda: [f() for f in calls])
+        keep.extend(calls)          # the tensors the closures captured outlive their use on the other stream
+    else:
+        for f in calls:
+            f()
+
+
+def _conv_operand(w: torch.Tensor) -> torch.Tensor:
+    """Patch-embedding conv weight [D, 3, p, p] -> the patch GEMM's bf16 operand [D, Kp]: K = 3 p p zero-padded to 64s"""
+    D, K = w.shape[0], w[0].numel()
+    Kp = (K + 63) // 64 * 64
+    wc = torch.zeros((D, Kp), dtype=F32, device=w.device)
+    wc[:, :K] = w.detach().reshape(D, K).float()
+    conv = torch.empty((D, Kp), dtype=BF16, device=w.device)
+    ops.cast_bf16(wc, conv)
+    return conv
+
+
+def _embed_forward(model, frozen, imgs, temporal):
+    """Patch embedding as a GEMM (conv1: kernel = stride = patch, no bias; vit_clip.py:436), class token, positional / temporal
+    embeddings and ln_pre, N = G G + 1 tokens per frame.  Consumes the blending armed for this forward.  Returns
+    (tok, x0 [B*T*N, D] f32, mean0, rstd0, tmp): what ``_embed_backward`` reads, around the residual stream's first value."""
+    B, C, T, Hh, Ww = imgs.shape
+    D, p = model.width, model.patch_size
+    G = Hh // p
+    N = G * G + 1
+    BT, M = B * T, B * T * N
+    dev = imgs.device
+    Kp = frozen["conv"].shape[1]
+    A = _empty((BT * G * G, Kp), BF16, dev)
+    blend, model._blend_now = model._blend_now, None
+    if blend is not None:    # Mixup / Cutmix applied while gathering: the blended clip batch is never written
+        ops.patchify_blend(imgs, A, B, T, Hh, Ww, p, Kp, *model._norm_now, blend=blend)
+    else:
+        ops.patchify(imgs, A, B, T, Hh, Ww, p, Kp, *model._norm_now)
+    tok = _empty((BT * G * G, D), BF16, dev)
+    ops.gemm(A, frozen["conv"], ops.EPI_BF16, tok)
+    del A
+    x0 = _empty((M, D), F32, dev)
+    mean0, rstd0 = _empty((M,), F32, dev), _empty((M,), F32, dev)
+    tmp = temporal.detach().reshape(T, D).float().contiguous()
+    ops.embed_ln(tok, frozen["cls"], frozen["pos"], tmp, frozen["gpre"], frozen["bpre"], x0, mean0, rstd0, B, T, N, D)
+    return tok, x0, mean0, rstd0, tmp
+
+
+def _ln_post_forward(x, lnp_w, lnp_b, BT, P):
+    """ln_post on the class rows only (LayerNorm is per-row; vit_clip.py:452-453): row 0 of every frame of an fp32 stream with
+    P rows per frame.  Returns (y [BT, D] f32, gw, meanp, rstdp)."""
+    D, dev = x.shape[1], x.device
+    gw, gb = lnp_w.detach().float().contiguous(), lnp_b.detach().float().contiguous()
+    y = _empty((BT, D), F32, dev)
+    meanp, rstdp = _empty((BT,), F32, dev), _empty((BT,), F32, dev)
+    ops.layernorm_fwd(x, gw, gb, BT, D, P * D, y_f32=y, mean=meanp, rstd=rstdp)
+    return y, gw, meanp, rstdp
+
+
+def _ln_post_backward(dy, s, dgw, dgb, BT, P):
+    """ln_post backward into a [BT*P, D] bf16 gradient: it touches the class rows only, every other row of the top gradient is zero"""
+    D = dy.shape[1]
+    dxb = torch.zeros((BT * P, D), dtype=BF16, device=dy.device)
+    ops.layernorm_bwd(dy, s["xL"], s["gw"], s["meanp"], s["rstdp"], BT, D, lddy=D, ldx=P * D, lddx=P * D,
+                      dx_bf16=dxb, dgamma=dgw, dbeta=dgb)
+    return dxb
+
+
+class _GradBufs:
+    """Gradient buffers of one backward (fp32; every kernel ACCUMULATES into them).  With ``grad_in_place`` (set by
+    dist.build_optimizer for the flat-buffer optimizer) the kernels add straight into the existing ``param.grad`` views of
+    the flat gradient buffer and autograd gets None for those inputs: no temporary zero-filled tensors and no 147 small
+    accumulate kernels per step."""
+
+    def __init__(self, model, params, dev):
+        self.model, self.params, self.dev = model, params, dev
+        self.out: List[Optional[torch.Tensor]] = [None] * len(params)
+        self.in_place = [False] * len(params)
+        self.per = 0
+
+    def buf(self, k):
+        p_ = self.params[k]
+        if (self.model.grad_in_place and p_.requires_grad and p_.grad is not None and p_.grad.dtype == F32
+                and p_.grad.is_contiguous() and p_.grad.device == self.dev):
+            self.in_place[k] = True
+            g = p_.grad
+        else:
+            g = torch.zeros_like(p_, dtype=F32)
+        self.out[k] = g
+        return g
+
+    def layers(self, L, names):
+        """``[{adapter: {leaf: buffer}}]`` per block, for blocks that carry the adapters ``names`` in parameter order"""
+        self.per = per = 4 * len(names)
+        layer_grads = []
+        for i in range(L):
+            lg = {}
+            for j, a in enumerate(names):
+                k = 3 + i * per + j * 4
+                lg[a] = {leaf: self.buf(k + e) for e, leaf in enumerate(_ADAPTER_LEAVES)}
+            layer_grads.append(lg)
+        return layer_grads
+
+    def layer_ready(self, i):
+        """Every kernel that accumulates into the gradients of layers >= i has been QUEUED (adapter weight gradients on the
+        detached stream): the data-parallel optimizer may start reducing that slice of the flat gradient buffer behind events
+        on these streams, while the backward of layers < i still runs."""
+        hook = self.model.grad_ready_hook
+        if hook is not None:
+            k0 = 3 + i * self.per
+            hook(i, all(self.in_place[k0:k0 + self.per]), _Fork.streams(self.dev))
+
+
+def _embed_backward(gb: _GradBufs, frozen, s, dxb, keep: list, B, T, N, D):
+    """The tail of a backward: the stem's gradient (dxb [B*T*N, D] bf16 -> temporal_embedding), the join with the detached
+    weight-gradient stream, and the tuple autograd gets: None for the three non-tensor inputs and for every frozen or
+    in-place parameter, the buffer in the parameter's dtype otherwise."""
+    dtmp = gb.buf(0)
+    ops.embed_bwd(dxb, s["tok"], frozen["cls"], frozen["pos"], s["tmp"], frozen["gpre"], s["mean0"], s["rstd0"],
+                  dtmp.view(T, D), B, T, N, D)
+    grads_out = gb.out
+    grads_out[0] = dtmp.view(1, T, D)
+    _Fork.join_detached(gb.dev)       # every weight gradient is in place before autograd hands them on
+    keep.clear()
+    for k, p_ in enumerate(gb.params):
+        if not p_.requires_grad or gb.in_place[k]:
+            grads_out[k] = None
+        elif grads_out[k] is not None and grads_out[k].dtype != p_.dtype:
+            grads_out[k] = grads_out[k].to(p_.dtype)
+    return (None, None, None) + tuple(grads_out)
+
+
+# ----------------------------------------------------------------------------------------------
 # whole backbone as one autograd node
 # ----------------------------------------------------------------------------------------------
 class _BackboneFn(torch.autograd.Function):
@@ -839,33 +979,8 @@ class _BackboneFn(torch.autograd.Function):
         # grad mode decides whether the per-block contexts (~2 GB per ViT-B layer at 64 clips) are kept
         need_grad = grad_enabled and any(ctx.needs_input_grad)
         frozen = model._frozen_operands()
-        staged_bias = model._stage_adapters(frozen, params)   # ONE launch: all 36 adapters' weights -> bf16 operands (+ biases)
-        adp = []
-        for i in range(L):
-            d = {}
-            for j, a in enumerate(_ADAPTERS):
-                k = 3 + (i * 3 + j) * 4
-                if a == "MLP_Adapter":      # shares the frozen MLP's GEMMs (concatenated operands)
-                    frozen["blocks"][i].stage_mlp_bias(params[k + 1], params[k + 3], copy_b1=not staged_bias)
-                else:
-                    d[a] = _AdapterW(params[k], params[k + 1], params[k + 2], params[k + 3],
-                                     bufs=frozen["blocks"][i].small[a])
-            adp.append(d)
-        # patch embedding as a GEMM (conv1: kernel = stride = patch, no bias; vit_clip.py:436)
-        Kp = frozen["conv"].shape[1]
-        A = _empty((BT * G * G, Kp), BF16, dev)
-        blend, model._blend_now = model._blend_now, None
-        if blend is not None:    # Mixup / Cutmix applied while gathering: the blended clip batch is never written
-            ops.patchify_blend(imgs, A, B, T, Hh, Ww, p, Kp, *model._norm_now, blend=blend)
-        else:
-            ops.patchify(imgs, A, B, T, Hh, Ww, p, Kp, *model._norm_now)
-        tok = _empty((BT * G * G, D), BF16, dev)
-        ops.gemm(A, frozen["conv"], ops.EPI_BF16, tok)
-        del A
-        x = _empty((M, D), F32, dev)
-        mean0, rstd0 = _empty((M,), F32, dev), _empty((M,), F32, dev)
-        tmp = temporal.detach().reshape(T, D).float().contiguous()
-        ops.embed_ln(tok, frozen["cls"], frozen["pos"], tmp, frozen["gpre"], frozen["bpre"], x, mean0, rstd0, B, T, N, D)
+        adp = model._stage_adapters(frozen, params)   # ONE launch: all 36 adapters' weights -> bf16 operands (+ biases)
+        tok, x, mean0, rstd0, tmp = _embed_forward(model, frozen, imgs, temporal)
         # blocks
         ctxs: List[Optional[dict]] = []
         training = model.training
@@ -925,49 +1040,20 @@ class _BackboneFn(torch.autograd.Function):
         model = ctx.model
         B, T, N, H, D, L = ctx.dims
         s = ctx.saved
-        BT, M = B * T, B * T * N
+        BT = B * T
         dev = dout.device
         frozen = model._frozen_operands()
-        params = s["params"]
-        # Gradient buffers (fp32; every kernel ACCUMULATES into them).  With `grad_in_place` (set by
-        # dist.build_optimizer for the flat-buffer optimizer) the kernels add straight into the existing
-        # `param.grad` views of the flat gradient buffer and autograd gets None for those inputs: no
-        # temporary zero-filled tensors and no 147 small accumulate kernels per step.
-        grads_out: List[Optional[torch.Tensor]] = [None] * len(params)
-        in_place = [False] * len(params)
-
-        def buf(k):
-            p_ = params[k]
-            if (model.grad_in_place and p_.requires_grad and p_.grad is not None and p_.grad.dtype == F32
-                    and p_.grad.is_contiguous() and p_.grad.device == dev):
-                in_place[k] = True
-                return p_.grad
-            return torch.zeros_like(p_, dtype=F32)
-
-        layer_grads = []
-        for i in range(L):
-            lg = {}
-            for j, a in enumerate(_ADAPTERS):
-                k = 3 + (i * 3 + j) * 4
-                lg[a] = {}
-                for e, leaf in enumerate(_ADAPTER_LEAVES):
-                    g = buf(k + e)
-                    lg[a][leaf] = g
-                    grads_out[k + e] = g
-            layer_grads.append(lg)
-        dgw, dgb = buf(1), buf(2)
+        gbufs = _GradBufs(model, s["params"], dev)
+        layer_grads = gbufs.layers(L, model._adapter_names)
+        dgw, dgb = gbufs.buf(1), gbufs.buf(2)
         dy = dout.permute(0, 2, 1).reshape(BT, D).contiguous().float()
-        # ln_post backward touches the class rows only; every other row of the top gradient is zero
         if s["top"]:        # the last block takes the class rows' gradient as it is: [B*T, D]
             dxb = _empty((BT, D), BF16, dev)
             ops.layernorm_bwd(dy, s["xL"], s["gw"], s["meanp"], s["rstdp"], BT, D, lddy=D, ldx=D, lddx=D,
                               dx_bf16=dxb, dgamma=dgw, dbeta=dgb)
         else:
-            dxb = torch.zeros((M, D), dtype=BF16, device=dev)
-            ops.layernorm_bwd(dy, s["xL"], s["gw"], s["meanp"], s["rstdp"], BT, D, lddy=D, ldx=N * D, lddx=N * D,
-                              dx_bf16=dxb, dgamma=dgw, dbeta=dgb)
+            dxb = _ln_post_backward(dy, s, dgw, dgb, BT, N)
         keep: list = []        # tensors the detached weight-gradient stream still reads; dropped after join_detached
-        hook = model.grad_ready_hook
         blk_bwd = _block_backward
         if model.variant == 'aim':
             from .aim_variant import aim_block_backward as blk_bwd
@@ -984,31 +1070,17 @@ class _BackboneFn(torch.autograd.Function):
                 # main stream is ordered behind the detached one before it can re-use the blocks)
                 _Fork.join_detached(dev)
                 keep.clear()
-            if hook is not None:
-                # every kernel that accumulates into the gradients of layers >= i has been QUEUED (adapter weight
-                # gradients on the detached stream): the data-parallel optimizer may start reducing that slice of the
-                # flat gradient buffer behind events on these streams, while the backward of layers < i still runs
-                k0 = 3 + i * 12
-                hook(i, all(in_place[k0:k0 + 12]), _Fork.streams(dev))
-        dtmp = buf(0)
-        ops.embed_bwd(dxb, s["tok"], frozen["cls"], frozen["pos"], s["tmp"], frozen["gpre"], s["mean0"], s["rstd0"],
-                      dtmp.view(T, D), B, T, N, D)
-        grads_out[0] = dtmp.view(1, T, D)
-        grads_out[1], grads_out[2] = dgw, dgb
-        _Fork.join_detached(dev)       # every weight gradient is in place before autograd hands them on
-        keep.clear()
-        for k, p_ in enumerate(params):
-            if not p_.requires_grad or in_place[k]:
-                grads_out[k] = None
-            elif grads_out[k] is not None and grads_out[k].dtype != p_.dtype:
-                grads_out[k] = grads_out[k].to(p_.dtype)
+            gbufs.layer_ready(i)
+        grads = _embed_backward(gbufs, frozen, s, dxb, keep, B, T, N, D)
         ctx.saved = None
-        return (None, None, None) + tuple(grads_out)
+        return grads
 
 
 @BACKBONES.register_module()
 class ViT_CLIP(nn.Module):
     """ViT definition in CLIP image encoder + AIM adapters (reference vit_clip.py:327-458)."""
+
+    _adapter_names = _ADAPTERS      # the adapters of a block, in parameter order (ViT_CLIP_ZEROI2V: its own set)
 
     def __init__(self, input_resolution: int, num_frames: int, patch_size: int, width: int, layers: int, heads: int,
                  drop_path_rate, adapter_scale=0.5, pretrained=None, shift=False, checkpoint=False):
@@ -1136,20 +1208,15 @@ class ViT_CLIP(nn.Module):
         key = tuple((p.data_ptr(), p._version) for p in self._frozen_params())
         if self._frozen_cache is not None and self._frozen_cache[0] == key:
             return self._frozen_cache[1]
-        D, p = self.width, self.patch_size
-        K = 3 * p * p
-        Kp = (K + 63) // 64 * 64
-        dev = self.conv1.weight.device
-        wc = torch.zeros((D, Kp), dtype=F32, device=dev)
-        wc[:, :K] = self.conv1.weight.detach().reshape(D, K).float()
-        conv = torch.empty((D, Kp), dtype=BF16, device=dev)
-        ops.cast_bf16(wc, conv)
         f = lambda t: t.detach().float().contiguous()
-        out = dict(conv=conv, cls=f(self.class_embedding), pos=f(self.positional_embedding),
+        out = dict(conv=_conv_operand(self.conv1.weight), cls=f(self.class_embedding), pos=f(self.positional_embedding),
                    gpre=f(self.ln_pre.weight), bpre=f(self.ln_pre.bias),
-                   blocks=[_Frozen(b) for b in self.transformer.resblocks])
+                   blocks=[self._frozen_block(b) for b in self.transformer.resblocks])
         self._frozen_cache = (key, out)
         return out
+
+    def _frozen_block(self, blk):
+        return _Frozen(blk)
 
     def set_inference_precision(self, precision: str):
         """'bf16' | 'fp8': operand type of the large GEMMs in no-grad forwards (training always runs bf16)."""
@@ -1168,39 +1235,51 @@ class ViT_CLIP(nn.Module):
 
     def _stage_adapters(self, frozen, params):
         """Re-cast every adapter weight (fp32 master) into its persistent bf16 operand buffers with one
-        ``aim_cast_multi`` launch.  The table of raw pointers is rebuilt only when a tensor moved."""
+        ``aim_cast_multi`` launch.  The table of raw pointers is rebuilt only when a tensor moved.  Returns the per-block
+        ``{name: _AdapterW}``; the MLP_Adapter shares the frozen MLP's GEMMs (concatenated operands) and has no entry."""
+        names = self._adapter_names
+        per = 4 * len(names)
+        at = lambda i, j: 3 + i * per + j * 4
         srcs = []
         for i in range(self.layers):
-            for j, a in enumerate(_ADAPTERS):
-                k = 3 + (i * 3 + j) * 4
-                srcs += [params[k], params[k + 2]]
-                if a == "MLP_Adapter":
-                    srcs.append(params[k + 1])
+            for j, a in enumerate(names):
+                k = at(i, j)
+                srcs += [params[k], params[k + 2]] + ([params[k + 1]] if a == "MLP_Adapter" else [])
         ok = all(p.dtype == F32 and p.is_contiguous() for p in srcs)
-        key = tuple(p.data_ptr() for p in srcs) + (id(frozen),)
-        if ok and (self._cast_table is None or self._cast_table[0] != key):
-            entries = []
-            for i in range(self.layers):
-                for j, a in enumerate(_ADAPTERS):
-                    k = 3 + (i * 3 + j) * 4
-                    entries += frozen["blocks"][i].cast_entries(a, params[k].detach(), params[k + 2].detach(),
-                                                                params[k + 1].detach() if a == "MLP_Adapter" else None)
-            self._cast_table = (key, ops.CastTable(entries, srcs[0].device))
         if ok:
+            key = tuple(p.data_ptr() for p in srcs) + (id(frozen),)
+            if self._cast_table is None or self._cast_table[0] != key:
+                entries = []
+                for i in range(self.layers):
+                    for j, a in enumerate(names):
+                        k = at(i, j)
+                        entries += frozen["blocks"][i].cast_entries(a, params[k].detach(), params[k + 2].detach(),
+                                                                    params[k + 1].detach() if a == "MLP_Adapter" else None)
+                self._cast_table = (key, ops.CastTable(entries, srcs[0].device))
             self._cast_table[1].run()
-            return True
-        for i in range(self.layers):           # generic path (non-fp32 / non-contiguous masters)
-            for j, a in enumerate(_ADAPTERS):
-                k = 3 + (i * 3 + j) * 4
-                for src, dst, tr in frozen["blocks"][i].cast_entries(a, params[k].detach().float().contiguous(),
-                                                                     params[k + 2].detach().float().contiguous()):
-                    ops.cast_bf16(src, dst, transpose=tr)
-        return False
+        else:               # generic path (non-fp32 / non-contiguous masters)
+            for i in range(self.layers):
+                for j, a in enumerate(names):
+                    k = at(i, j)
+                    for src, dst, tr in frozen["blocks"][i].cast_entries(a, params[k].detach().float().contiguous(),
+                                                                         params[k + 2].detach().float().contiguous()):
+                        ops.cast_bf16(src, dst, transpose=tr)
+        adp = []
+        for i in range(self.layers):
+            d = {}
+            for j, a in enumerate(names):
+                k = at(i, j)
+                if a == "MLP_Adapter":
+                    frozen["blocks"][i].stage_mlp_bias(params[k + 1], params[k + 3], copy_b1=not ok)
+                else:
+                    d[a] = _AdapterW(params[k], params[k + 1], params[k + 2], params[k + 3], bufs=frozen["blocks"][i].small[a])
+            adp.append(d)
+        return adp
 
     def _trainable_list(self):
         ps = [self.temporal_embedding, self.ln_post.weight, self.ln_post.bias]
         for blk in self.transformer.resblocks:
-            for a in _ADAPTERS:
+            for a in self._adapter_names:
                 m = getattr(blk, a)
                 ps += [m.D_fc1.weight, m.D_fc1.bias, m.D_fc2.weight, m.D_fc2.bias]
         return ps
@@ -1238,15 +1317,22 @@ class ViT_CLIP(nn.Module):
         return (u < keep_d).to(F32) * fac_d
 
     # ---- forward --------------------------------------------------------------------------------
-    def forward(self, x: torch.Tensor):
+    def _take_blend_check_clip(self, x: torch.Tensor, name: str):
+        """First half of every CLIP-family ``forward``: takes the blending armed for this call (one shot, whatever follows),
+        then checks device and clip shape.  ``name``: the class the device error names.  Returns the blending."""
         blend, self._blend_next = self._blend_next, None
         if not x.is_cuda:
-            raise RuntimeError("aim_amd.ViT_CLIP runs on MI355X only (HIP kernels); there is no CPU fallback")
+            raise RuntimeError(f"aim_amd.{name} runs on MI355X only (HIP kernels); there is no CPU fallback")
         B, C, T, H, W = x.shape
         if T != self.num_frames:
             raise ValueError(f"expected {self.num_frames} frames, got {T}")   # reference: einops error at :443
         if C != 3 or H != self.input_resolution or W != self.input_resolution:
             raise ValueError(f"expected input [B,3,{T},{self.input_resolution},{self.input_resolution}], got {tuple(x.shape)}")
+        return blend
+
+    def _arm_clip(self, x: torch.Tensor, blend):
+        """Second half, behind a subclass's own limits: the clip as the patch gather takes it, with the normalisation and
+        the blending of this call armed for it (``_norm_now``, ``_blend_now``)."""
         if x.dtype == torch.float16:
             x = x.float()
         x = x.contiguous()
@@ -1256,10 +1342,15 @@ class ViT_CLIP(nn.Module):
         self._norm_mean = self._norm_std = None
         if x.dtype == torch.uint8 and self._norm_now[0] is None:
             raise TypeError("uint8 clips need a GPUNormalize module hook on the backbone (module_hooks.py:35-87)")
+        B = x.shape[0]
         if blend is not None and (x.dtype not in (torch.float32, torch.uint8) or blend.partner.numel() != B):
             raise TypeError(f"a fused blending needs float32 or uint8 clips and one partner per clip, got {x.dtype} and "
                             f"{blend.partner.numel()} partners for {B} clips")
         self._blend_now = blend
+        return x
+
+    def forward(self, x: torch.Tensor):
+        x = self._arm_clip(x, self._take_blend_check_clip(x, "ViT_CLIP"))
         if self.precision == 'fp32':
             from .fp32_path import _BackboneFn32, forward_f32
             if torch.is_grad_enabled() and any(p.requires_grad for p in self._trainable_list()):

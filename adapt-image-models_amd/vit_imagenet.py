@@ -25,7 +25,7 @@ import torch
 from torch import nn
 
 from . import ops
-from .backbone import BF16, F32, _AUX_FRAG, _AUX_GRAD, _AdapterW, _Frozen, _empty, _cast
+from .backbone import BF16, F32, _AUX_FRAG, _AUX_GRAD, _AdapterW, _Frozen, _conv_operand, _empty, _cast
 from .registry import BACKBONES
 
 _LOG = logging.getLogger("aim_amd")
@@ -554,18 +554,10 @@ class ViT_ImageNet(nn.Module):
             key += (self.weights_epoch, FlatAdamW.generation)
         if self._frozen_cache is not None and self._frozen_cache[0] == key:
             return self._frozen_cache[1]
-        D, p = self.embed_dim, self.patch_size
-        K = 3 * p * p
-        Kp = (K + 63) // 64 * 64
-        w = self.patch_embed.proj.weight
-        dev = w.device
-        wc = torch.zeros((D, Kp), dtype=F32, device=dev)
-        wc[:, :K] = w.detach().reshape(D, K).float()
-        conv = torch.empty((D, Kp), dtype=BF16, device=dev)
-        ops.cast_bf16(wc, conv)
-        b = self.patch_embed.proj.bias
+        D = self.embed_dim
+        w, b = self.patch_embed.proj.weight, self.patch_embed.proj.bias
         f = lambda t: t.detach().float().contiguous()
-        out = dict(conv=conv, conv_b=f(b) if b is not None else torch.zeros(D, dtype=F32, device=dev),
+        out = dict(conv=_conv_operand(w), conv_b=f(b) if b is not None else torch.zeros(D, dtype=F32, device=w.device),
                    cls=f(self.cls_token).view(D), pos=f(self.pos_embed).view(-1, D),
                    blocks=[_FrozenIN(blk) for blk in self.blocks])
         self._frozen_cache = (key, out)

@@ -29,8 +29,9 @@ from typing import Dict, List, Optional
 import torch
 
 from . import ops
-from .backbone import (_ADAPTER_LEAVES, _AUX_GRAD, _DETACH_WGRAD, _DP_RESERVE, BF16, F32, ViT_CLIP, _AdapterW, _Arena, _empty,
-                       _Fork, _Frozen, _mlp_adapter_backward, _mlp_adapter_forward)
+from .backbone import (_AUX_GRAD, _DP_RESERVE, BF16, F32, ViT_CLIP, _AdapterW, _Arena, _embed_backward, _embed_forward, _empty,
+                       _Fork, _Frozen, _GradBufs, _ln_post_backward, _ln_post_forward, _mlp_adapter_backward,
+                       _mlp_adapter_forward, _wgrads_beside)
 from .registry import BACKBONES
 
 _LOG = logging.getLogger("aim_amd")
@@ -45,19 +46,6 @@ def head_shifts(T: int, H: int):
     if len(tab) > H:
         raise ValueError(f"num_frames={T} shifts heads 0..{len(tab) - 1}; the model has {H} heads")
     return tuple(tab) + (0,) * (H - len(tab))
-
-
-def _wgrads_beside(fork: _Fork, calls: list, keep: Optional[list]):
-    """The block's weight-gradient launches: on the detached stream behind everything the main stream has queued (nobody
-    downstream waits for them until ``_Fork.join_detached``), or inline when the streams are switched off."""
-    if not calls:
-        return
-    if fork.enabled and _DETACH_WGRAD and keep is not None:
-        fork.run_beside(lambda: [f() for f in calls])
-        keep.extend(calls)          # the tensors the closures captured outlive their use on the other stream
-    else:
-        for f in calls:
-            f()
 
 
 def _block_forward(x, fz: _Frozen, adp: Dict[str, _AdapterW], B, T, P, H, tcls: bool, shifts, dms1, dms2, save: bool):
@@ -194,22 +182,9 @@ class _ZeroI2VFn(torch.autograd.Function):
         temporal, lnp_w, lnp_b = params[0], params[1], params[2]
         need_grad = grad_enabled and any(ctx.needs_input_grad)
         frozen = model._frozen_operands()
-        adp = model._stage_adapters_z(frozen, params)
+        adp = model._stage_adapters(frozen, params)
         # patch embedding, class token, positional / temporal embeddings, ln_pre: ViT_CLIP's kernels, N tokens per frame
-        Kp = frozen["conv"].shape[1]
-        A = _empty((BT * G * G, Kp), BF16, dev)
-        blend, model._blend_now = model._blend_now, None
-        if blend is not None:
-            ops.patchify_blend(imgs, A, B, T, Hh, Ww, p, Kp, *model._norm_now, blend=blend)
-        else:
-            ops.patchify(imgs, A, B, T, Hh, Ww, p, Kp, *model._norm_now)
-        tok = _empty((BT * G * G, D), BF16, dev)
-        ops.gemm(A, frozen["conv"], ops.EPI_BF16, tok)
-        del A
-        x0 = _empty((BT * N, D), F32, dev)
-        mean0, rstd0 = _empty((BT * N,), F32, dev), _empty((BT * N,), F32, dev)
-        tmp = temporal.detach().reshape(T, D).float().contiguous()
-        ops.embed_ln(tok, frozen["cls"], frozen["pos"], tmp, frozen["gpre"], frozen["bpre"], x0, mean0, rstd0, B, T, N, D)
+        tok, x0, mean0, rstd0, tmp = _embed_forward(model, frozen, imgs, temporal)
         if tcls:        # once per forward: into the P-token layout (row 1 = the temporal class token's slot)
             x = _empty((BT * P, D), F32, dev)
             xv, x0v = x.view(BT, P, D), x0.view(BT, N, D)
@@ -229,11 +204,7 @@ class _ZeroI2VFn(torch.autograd.Function):
         for i in range(L):
             x, c = _block_forward(x, frozen["blocks"][i], adp[i], B, T, P, H, tcls, shifts, dp1[i], dp2[i], need_grad)
             ctxs.append(c)
-        # ln_post on the class rows only
-        gw, gb = lnp_w.detach().float().contiguous(), lnp_b.detach().float().contiguous()
-        y = _empty((BT, D), F32, dev)
-        meanp, rstdp = _empty((BT,), F32, dev), _empty((BT,), F32, dev)
-        ops.layernorm_fwd(x, gw, gb, BT, D, P * D, y_f32=y, mean=meanp, rstd=rstdp)
+        y, gw, meanp, rstdp = _ln_post_forward(x, lnp_w, lnp_b, BT, P)
         if need_grad:
             ctx.model, ctx.dims = model, (B, T, N, P, H, D, L)
             ctx.saved = dict(ctxs=ctxs, adp=adp, tok=tok, mean0=mean0, rstd0=rstd0, tmp=tmp, xL=x, gw=gw, meanp=meanp,
@@ -249,63 +220,26 @@ class _ZeroI2VFn(torch.autograd.Function):
         BT = B * T
         dev = dout.device
         frozen = model._frozen_operands()
-        params = s["params"]
-        names = model._adapter_names
-        grads_out: List[Optional[torch.Tensor]] = [None] * len(params)
-        in_place = [False] * len(params)
-
-        def buf(k):      # fp32, every kernel ACCUMULATES: straight into param.grad under dist.build_optimizer (grad_in_place)
-            p_ = params[k]
-            if (model.grad_in_place and p_.requires_grad and p_.grad is not None and p_.grad.dtype == F32
-                    and p_.grad.is_contiguous() and p_.grad.device == dev):
-                in_place[k] = True
-                return p_.grad
-            return torch.zeros_like(p_, dtype=F32)
-
-        per = 4 * len(names)
-        layer_grads = []
-        for i in range(L):
-            lg = {}
-            for j, a in enumerate(names):
-                k = 3 + i * per + j * 4
-                lg[a] = {}
-                for e, leaf in enumerate(_ADAPTER_LEAVES):
-                    lg[a][leaf] = grads_out[k + e] = buf(k + e)
-            layer_grads.append(lg)
-        dgw, dgb = buf(1), buf(2)
+        gbufs = _GradBufs(model, s["params"], dev)
+        layer_grads = gbufs.layers(L, model._adapter_names)
+        dgw, dgb = gbufs.buf(1), gbufs.buf(2)
         dy = dout.permute(0, 2, 1).reshape(BT, D).contiguous().float()
-        dxb = torch.zeros((BT * P, D), dtype=BF16, device=dev)          # ln_post touches the class rows only
-        ops.layernorm_bwd(dy, s["xL"], s["gw"], s["meanp"], s["rstdp"], BT, D, lddy=D, ldx=P * D, lddx=P * D,
-                          dx_bf16=dxb, dgamma=dgw, dbeta=dgb)
+        dxb = _ln_post_backward(dy, s, dgw, dgb, BT, P)
         keep: list = []
-        hook = model.grad_ready_hook
         for i in reversed(range(L)):
             dxb = _block_backward(dxb, s["ctxs"][i], frozen["blocks"][i], s["adp"][i], layer_grads[i], B, T, P, H, tcls,
                                   s["shifts"], keep)
             s["ctxs"][i] = None
-            if hook is not None:
-                k0 = 3 + i * per
-                hook(i, all(in_place[k0:k0 + per]), _Fork.streams(dev))
+            gbufs.layer_ready(i)
         if tcls:        # once per backward: back to the embedding's N tokens per frame (the slot's row is zero)
             d0 = _empty((BT, N, D), BF16, dev)
             dv = dxb.view(BT, P, D)
             d0[:, 0] = dv[:, 0]
             d0[:, 1:] = dv[:, 2:]
             dxb = d0.view(BT * N, D)
-        dtmp = buf(0)
-        ops.embed_bwd(dxb, s["tok"], frozen["cls"], frozen["pos"], s["tmp"], frozen["gpre"], s["mean0"], s["rstd0"],
-                      dtmp.view(T, D), B, T, N, D)
-        grads_out[0] = dtmp.view(1, T, D)
-        grads_out[1], grads_out[2] = dgw, dgb
-        _Fork.join_detached(dev)       # every weight gradient is in place before autograd hands them on
-        keep.clear()
-        for k, p_ in enumerate(params):
-            if not p_.requires_grad or in_place[k]:
-                grads_out[k] = None
-            elif grads_out[k] is not None and grads_out[k].dtype != p_.dtype:
-                grads_out[k] = grads_out[k].to(p_.dtype)
+        grads = _embed_backward(gbufs, frozen, s, dxb, keep, B, T, N, D)
         ctx.saved = None
-        return (None, None, None) + tuple(grads_out)
+        return grads
 
 
 @BACKBONES.register_module()
@@ -340,56 +274,6 @@ class ViT_CLIP_ZEROI2V(ViT_CLIP):
             raise NotImplementedError("ViT_CLIP_ZEROI2V has no fp32 verification mode")
         return super().set_precision(precision)
 
-    def _trainable_list(self):
-        ps = [self.temporal_embedding, self.ln_post.weight, self.ln_post.bias]
-        for blk in self.transformer.resblocks:
-            for a in self._adapter_names:
-                m = getattr(blk, a)
-                ps += [m.D_fc1.weight, m.D_fc1.bias, m.D_fc2.weight, m.D_fc2.bias]
-        return ps
-
-    def _stage_adapters_z(self, frozen, params):
-        """Every adapter's fp32 master weights -> its persistent bf16 operand buffers (one ``aim_cast_multi`` launch; the
-        table of raw pointers is rebuilt only when a tensor moved).  Returns the per-block ``_AdapterW``."""
-        names = self._adapter_names
-        per = 4 * len(names)
-        at = lambda i, j: 3 + i * per + j * 4
-        srcs = []
-        for i in range(self.layers):
-            for j, a in enumerate(names):
-                k = at(i, j)
-                srcs += [params[k], params[k + 2]] + ([params[k + 1]] if a == "MLP_Adapter" else [])
-        ok = all(p.dtype == F32 and p.is_contiguous() for p in srcs)
-        if ok:
-            key = tuple(p.data_ptr() for p in srcs) + (id(frozen),)
-            if self._cast_table is None or self._cast_table[0] != key:
-                entries = []
-                for i in range(self.layers):
-                    for j, a in enumerate(names):
-                        k = at(i, j)
-                        entries += frozen["blocks"][i].cast_entries(a, params[k].detach(), params[k + 2].detach(),
-                                                                    params[k + 1].detach() if a == "MLP_Adapter" else None)
-                self._cast_table = (key, ops.CastTable(entries, srcs[0].device))
-            self._cast_table[1].run()
-        else:               # generic path (non-fp32 / non-contiguous masters)
-            for i in range(self.layers):
-                for j, a in enumerate(names):
-                    k = at(i, j)
-                    for src, dst, tr in frozen["blocks"][i].cast_entries(a, params[k].detach().float().contiguous(),
-                                                                         params[k + 2].detach().float().contiguous()):
-                        ops.cast_bf16(src, dst, transpose=tr)
-        adp = []
-        for i in range(self.layers):
-            d = {}
-            for j, a in enumerate(names):
-                k = at(i, j)
-                if a == "MLP_Adapter":
-                    frozen["blocks"][i].stage_mlp_bias(params[k + 1], params[k + 3], copy_b1=not ok)
-                else:
-                    d[a] = _AdapterW(params[k], params[k + 1], params[k + 2], params[k + 3], bufs=frozen["blocks"][i].small[a])
-            adp.append(d)
-        return adp
-
     def _drop_masks_z(self, P, N, training, dev):
         """DropPath factor times adapter scale per TOKEN index (timm's mask has shape (x.shape[0], 1, 1) and the reference's
         x is [tokens, BT, D]): per block the S_Adapter's over the P tokens, then the MLP_Adapter's over the N that remain --
@@ -413,27 +297,10 @@ class ViT_CLIP_ZEROI2V(ViT_CLIP):
         return m[:, :P].contiguous(), m[:, P:].contiguous()
 
     def forward(self, x: torch.Tensor):
-        blend, self._blend_next = self._blend_next, None
-        if not x.is_cuda:
-            raise RuntimeError("aim_amd.ViT_CLIP_ZEROI2V runs on MI355X only (HIP kernels); there is no CPU fallback")
-        B, C, T, H, W = x.shape
-        if T != self.num_frames:
-            raise ValueError(f"expected {self.num_frames} frames, got {T}")
-        if C != 3 or H != self.input_resolution or W != self.input_resolution:
-            raise ValueError(f"expected input [B,3,{T},{self.input_resolution},{self.input_resolution}], got {tuple(x.shape)}")
-        N = (H // self.patch_size) ** 2 + 1
+        blend = self._take_blend_check_clip(x, "ViT_CLIP_ZEROI2V")
+        N = (x.shape[3] // self.patch_size) ** 2 + 1
         if N + int(self.with_t_cls_token) > 288:
             raise ValueError(f"{N + int(self.with_t_cls_token)} tokens per frame: the attention kernels take at most 288")
-        if x.dtype == torch.float16:
-            x = x.float()
-        x = x.contiguous()
-        self._norm_now = (self._norm_mean, self._norm_std) if x.dtype == torch.uint8 else (None, None)
-        self._norm_mean = self._norm_std = None
-        if x.dtype == torch.uint8 and self._norm_now[0] is None:
-            raise TypeError("uint8 clips need a GPUNormalize module hook on the backbone (module_hooks.py:35-87)")
-        if blend is not None and (x.dtype not in (torch.float32, torch.uint8) or blend.partner.numel() != B):
-            raise TypeError(f"a fused blending needs float32 or uint8 clips and one partner per clip, got {x.dtype} and "
-                            f"{blend.partner.numel()} partners for {B} clips")
-        self._blend_now = blend
+        x = self._arm_clip(x, blend)
         y = _ZeroI2VFn.apply(self, torch.is_grad_enabled(), x, *self._trainable_list())     # [B, D, T]
         return y.unsqueeze(-1).unsqueeze(-1)

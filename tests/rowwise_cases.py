@@ -524,8 +524,8 @@ KINDS["embed_ln"] = (embed_ln_inputs, embed_ln_expected, embed_ln_emulate, embed
 
 
 # ---- layernorm_bwd -------------------------------------------------------------------------------------------------------------
-# forms: "strided" (every operand in a wider buffer, lddres != lddx), "dense", "classrow" (backbone.py:805-807: all rows
-# without dres, then the class rows again at stride N*D with dres at stride D), "zshift" (zeroi2v.py:156: row 1 of every
+# forms: "strided" (every operand in a wider buffer, lddres != lddx), "dense", "classrow" (backbone.py:813-815: all rows
+# without dres, then the class rows again at stride N*D with dres at stride D), "zshift" (zeroi2v.py:144: row 1 of every
 # frame, inputs at stride P*D from a pointer one row in, dx at stride D)
 def _bwd_geom(p):
     form = p["form"]
