@@ -655,7 +655,10 @@ extern "C" int aim_gemm_f32(const aim_gemm_args* args, int epilogue, int batch, 
     AIM_CHECK_ARG((g.K % 4) == 0 && (g.lda % 4) == 0 && (g.ldw % 4) == 0 && ((g.strideA | g.strideW) % 4) == 0,
                   "gemm_f32: K, lda, ldw and the batch strides must be multiples of 4 (K=%d lda=%d ldw=%d)", g.K, g.lda, g.ldw);
     AIM_CHECK_ARG((((uintptr_t)g.A | (uintptr_t)g.W) & 15) == 0, "gemm_f32: operands must be 16-byte aligned");
+    AIM_CHECK_ARG(g.lda >= g.K && g.ldw >= g.K, "gemm_f32: lda < K or ldw < K (lda=%d ldw=%d K=%d)", g.lda, g.ldw, g.K);
     AIM_CHECK_ARG(g.ldo >= g.N, "gemm_f32: ldo < N");
+    AIM_CHECK_ARG(epilogue != EPI_F32 || ((!g.resid || g.ldr >= g.N) && (!g.vec || g.ldv == 0 || g.ldv >= g.N)),
+                  "gemm_f32: ldr < N, or ldv neither 0 (one row for every frame) nor >= N (ldr=%d ldv=%d N=%d)", g.ldr, g.ldv, g.N);
     if (g.af || g.at || g.vec || g.bt) AIM_CHECK_ARG(g.ntok > 0, "gemm_f32: ntok required with row factors");
     AIM_CHECK_ARG(batch == 1 || epilogue == EPI_BF16, "gemm_f32: batched problems take the linear epilogue only");
     AIM_CHECK_ARG(!g.out2 || (epilogue == EPI_ACT && g.ldo2 >= g.N), "gemm_f32: out2 (the fp32 pre-activation) goes with AIM_EPI_ACT, ldo2 >= N");
@@ -752,7 +755,8 @@ extern "C" int aim_patchify_f32(const void* imgs, int in_dtype, const float* mea
 extern "C" int aim_patchify_blend_f32(const void* imgs, int in_dtype, const float* mean3, const float* std3, float* A, int B,
                                       int T, int H, int W, int p, int Kp, const int* partner, int mode, float lam, float oml,
                                       int x1, int y1, int x2, int y2, void* stream) {
-    AIM_CHECK_ARG(B > 0 && T > 0 && p > 0 && H % p == 0 && W % p == 0 && Kp >= 3 * p * p, "patchify_blend_f32: bad shape");
+    AIM_CHECK_ARG(B > 0 && T > 0 && p > 0 && H % p == 0 && W % p == 0, "patchify_blend_f32: bad shape H=%d W=%d p=%d", H, W, p);
+    AIM_CHECK_ARG(Kp >= 3 * p * p && (Kp % 4) == 0, "patchify_blend_f32: Kp=%d must be >= 3*p*p and a multiple of 4", Kp);
     AIM_CHECK_ARG(imgs && A && ((!mean3) == (!std3)), "patchify_blend_f32: null pointer");
     if (aim_blend_check("patchify_blend_f32", partner, mode, H, W, x1, y1, x2, y2)) return 1;
     const AimBlend bl{partner, mode, lam, oml, x1, y1, x2, y2};

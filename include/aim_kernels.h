@@ -413,7 +413,9 @@ int aim_ce_soft(const float* score, const float* label, const float* class_weigh
  *                    n_split / act2 as above; out2 != NULL receives the f32 pre-activation acc + bias, ldo2 floats per row),
  *                    AIM_EPI_DACT (out = [rs *] acc * act'(aux): aux = that f32 pre-activation, ldaux floats per row; exact
  *                    erf / exp derivative; aux_grad / aux_frag are ignored), AIM_EPI_F32; batch > 1 (linear only) writes
- *                    item z at out + z * M * ldo.  K, lda, ldw multiples of 4.  replaces vit_clip.py:93-97,132-138,157,286,436.
+ *                    item z at out + z * M * ldo.  K, lda, ldw multiples of 4; lda, ldw >= K, ldo >= N, ldr >= N, and ldv
+ *                    either 0 (one row for every frame) or >= N: anything else is refused.
+ *                    replaces vit_clip.py:93-97,132-138,157,286,436.
  *   attn_fwd_f32   : softmax(q k^T / 8) v per (frame, head) on the fused f32 qkv rows [BT*N, 3D]; out [BT*N, D].  :139-156
  *   cls_attn_fwd_f32 : the same over the T class tokens of each clip (sequence T, batch B); qkv rows of the class tokens
  *                    are `row_stride` floats apart (N * 3D in the fused buffer); out [B*T, D].  :220-229
@@ -444,7 +446,8 @@ int aim_patchify_f32(const void* imgs, int in_dtype, const float* mean3, const f
                      int H, int W, int p, int Kp, void* stream);
 int aim_patchify_blend_f32(const void* imgs, int in_dtype, const float* mean3, const float* std3, float* A, int B, int T,
                            int H, int W, int p, int Kp, const int32_t* partner, int mode, float lam, float oml, int x1, int y1,
-                           int x2, int y2, void* stream);    /* aim_patchify_blend with an f32 patch matrix */
+                           int x2, int y2, void* stream);    /* aim_patchify_blend with an f32 patch matrix (Kp % 4 == 0, as
+                                                                  aim_patchify_f32 and the GEMM behind it require) */
 int aim_embed_ln_f32(const float* tok, const float* cls, const float* pos, const float* temporal, const float* gamma,
                      const float* beta, float* x, float* pre, float* mean, float* rstd, int B, int T, int N, int D, float eps,
                      void* stream);
