@@ -106,9 +106,10 @@ def _frozen_view(blk: WinResidualAttentionBlock):
                            d_model=blk.d_model, MLP_Adapter=blk.MLP_Adapter)
 
 
-def _block_forward(x, fz: _Frozen, adp: Dict[str, _AdapterW], B, T, N, P, H, window, f1, f2, f3, tokm, save: bool):
+def _block_forward(x, fz: _Frozen, adp: Dict[str, _AdapterW], B, T, N, P, H, window, f1, f2, f3, tokm, save: bool, shift=None):
     """x [B*T*P, D] f32 (P = N + 1 with the prompt: row N of every frame is its slot) -> x3, ctx.  f1, f2, f3 [B*T]: the
-    DropPath factors per frame (f2, f3 times the adapter scale); tokm [P]: 1 per token, 0 at the slot."""
+    DropPath factors per frame (f2, f3 times the adapter scale); tokm [P]: 1 per token, 0 at the slot.  shift: None or the
+    (st, sh, sw) by which this block's windows are shifted (aim_flash.py)."""
     dev = x.device
     M, D = x.shape
     BT, r = B * T, fz.r
@@ -124,7 +125,10 @@ def _block_forward(x, fz: _Frozen, adp: Dict[str, _AdapterW], B, T, N, P, H, win
     # ---- 2, 3: window attention on the patch rows, class-token attention on the class rows, into one [M, D] buffer
     at_ = _empty((M, D), BF16, dev)
     lse_w = _empty((BT, H, P), F32, dev)
-    ops.win_attn_fwd(qkv, at_, lse_w, B, T, N, H, window, P=P)
+    if shift is None:
+        ops.win_attn_fwd(qkv, at_, lse_w, B, T, N, H, window, P=P)
+    else:
+        ops.win_attn_fwd_shift(qkv, at_, lse_w, B, T, N, H, window, shift, P=P)
     ot, probs = _empty((BT, D), BF16, dev), _empty((B, H, T, T), F32, dev)
     ops.cls_attn_fwd(qkv, ot, probs, B, T, P, H)
     xv(at_)[:, 0] = ot
@@ -170,9 +174,10 @@ def _block_forward(x, fz: _Frozen, adp: Dict[str, _AdapterW], B, T, N, P, H, win
     return x3, c
 
 
-def _block_backward(dyb, c, fz: _Frozen, adp: Dict[str, _AdapterW], grads, B, T, N, P, H, window, keep: Optional[list]):
+def _block_backward(dyb, c, fz: _Frozen, adp: Dict[str, _AdapterW], grads, B, T, N, P, H, window, keep: Optional[list],
+                    shift=None):
     """dyb = d(loss)/d(x3) [M, D] bf16 with a zero slot row in every frame -> d(loss)/d(x) with the same property; the
-    adapters' gradients are accumulated into ``grads``."""
+    adapters' gradients are accumulated into ``grads``.  shift: what the block's forward was given."""
     dev = dyb.device
     M, D = dyb.shape
     BT, r = B * T, fz.r
@@ -227,7 +232,10 @@ def _block_backward(dyb, c, fz: _Frozen, adp: Dict[str, _AdapterW], grads, B, T,
     xv(dqkv)[:, 0] = 0
     if prompt:
         xv(dqkv)[:, N] = 0
-    ops.win_attn_bwd(c["qkv"], c["at"], dat, c["lse_w"], delta, dqkv, B, T, N, H, window, P=P)
+    if shift is None:
+        ops.win_attn_bwd(c["qkv"], c["at"], dat, c["lse_w"], delta, dqkv, B, T, N, H, window, P=P)
+    else:
+        ops.win_attn_bwd_shift(c["qkv"], c["at"], dat, c["lse_w"], delta, dqkv, B, T, N, H, window, shift, P=P)
     ops.cls_attn_bwd(c["qkv"], c["probs"], xv(dat)[:, 0].contiguous(), dqkv, B, T, P, H)
     del dat
     later.append(lambda: ops.wgrad(dtp, ta, gt["D_fc1.weight"], gt["D_fc1.bias"]))
@@ -274,16 +282,17 @@ class _FlashWinFn(torch.autograd.Function):
         if P != N:
             tokm[N] = 0
         window = clip_window(model.window_size, T, G)
+        shifts = [model._block_shift(i, T, G) for i in range(L)]
         ctxs: List[Optional[dict]] = []
         for i in range(L):
             x, c = _block_forward(x, frozen["blocks"][i], adp[i], B, T, N, P, H, window, fac[i, 0], fac[i, 1], fac[i, 2], tokm,
-                                  need_grad)
+                                  need_grad, shifts[i])
             ctxs.append(c)
         y, gw, meanp, rstdp = _ln_post_forward(x, lnp_w, lnp_b, BT, P)
         if need_grad:
             ctx.model, ctx.dims = model, (B, T, N, P, H, D, L)
             ctx.saved = dict(ctxs=ctxs, adp=adp, tok=tok, mean0=mean0, rstd0=rstd0, tmp=tmp, xL=x, gw=gw, meanp=meanp,
-                             rstdp=rstdp, params=params, window=window)
+                             rstdp=rstdp, params=params, window=window, shifts=shifts)
         return y.reshape(B, T, D).permute(0, 2, 1)      # '(b t) d -> b d t'
 
     @staticmethod
@@ -302,7 +311,7 @@ class _FlashWinFn(torch.autograd.Function):
         keep: list = []
         for i in reversed(range(L)):
             dxb = _block_backward(dxb, s["ctxs"][i], frozen["blocks"][i], s["adp"][i], layer_grads[i], B, T, N, P, H,
-                                  s["window"], keep)
+                                  s["window"], keep, s["shifts"][i])
             s["ctxs"][i] = None
             gbufs.layer_ready(i)
         if P != N:          # once per backward: back to the embedding's N tokens per frame (the slot's row is zero)
@@ -384,6 +393,10 @@ class AIM_FLASH_WIN(ViT_CLIP):
 
     def _frozen_block(self, blk):
         return _Frozen(_frozen_view(blk))
+
+    def _block_shift(self, i: int, T: int, G: int):
+        """the (st, sh, sw) of block i's windows on a T x G x G grid, or None: this class shifts none (aim_flash.py does)"""
+        return None
 
     def _drop_masks_w(self, BT, training, dev):
         """The three DropPath factors of every block per FRAME, ``[L, 3, BT]``, in the reference's draw order (:200, :215,

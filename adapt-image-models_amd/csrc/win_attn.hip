@@ -24,6 +24,10 @@
 // summation order (the tile order), each pass holds 32 / 64 accumulator VGPRs and 16 KiB of LDS, and the price is computing
 // s and dP twice (5 MFMA products against 3.5 per pass pair: 7 against 5).  Every patch token lies in exactly one window.
 //
+// The kernels are templates on SHIFT: false is the window partition above, true the box partition of shifted windows (AIM_FLASH's
+// odd blocks; the rule stands above the *_shift entry points at the end of the file).  Only win_item, win_row and the early exit
+// of a workgroup past a small box differ.
+//
 // Tails: streamed rows past S are zero-filled by the buffer bounds check (AIM_OOB) and their probabilities forced to 0; own
 // tokens past S load the window's last token and are not stored.
 #include "aim_common.h"
@@ -38,31 +42,55 @@ constexpr float C2 = 0.125f * LOG2E;      // 1/sqrt(dh) * log2(e): the softmax r
 struct WinGeom {
     int T, P, G, H;       // P: tokens per frame of the buffers (row stride); the grid's tokens are 1 .. G G
     int wt, wh, ww;       // window extents (after clipping)
-    int nh, nw, nW;       // windows along h and w, windows per clip
-    int S;
+    int nh, nw, nW;       // boxes along h and w, boxes per clip
+    int S;                // tokens of a whole window (the largest box)
+    int st, sh, sw;       // shifts (the *_shift entries; 0 otherwise)
 };
 
+// One sequence: the box [t0, t0 + wt) x [h0, h0 + eh) x [w0, w0 + ew) of the grid, S = wt eh ew tokens in (dt, dh, dw) row-major
+// order.  Unshifted: every box is a window (eh = wh, ew = ww, S = g.S).  Shifted: the rule above the *_shift entry points.
 struct WinItem {
     int b, h, t0, h0, w0;
+    int eh, ew, S;
 };
 
+// segment j of an axis of extent w cut at 0, s, s + w, s + 2 w, ...: its start and its length (s = 0: j w and w)
+__device__ __forceinline__ void axis_segment(int j, int w, int s, int G, int* start, int* len) {
+    const int a = j ? s + (j - 1) * w : 0;
+    const int e = s + j * w < G ? s + j * w : G;
+    *start = s ? a : j * w;
+    *len = s ? e - a : w;
+}
+
+template <bool SHIFT>
 __device__ __forceinline__ WinItem win_item(const WinGeom& g, int item) {
     WinItem it;
     it.h = item % g.H;
     const int bw = item / g.H, win = bw % g.nW;
     it.b = bw / g.nW;
     const int iw = win % g.nw, r = win / g.nw, ih = r % g.nh, itt = r / g.nh;
-    it.t0 = itt * g.wt;
-    it.h0 = ih * g.wh;
-    it.w0 = iw * g.ww;
+    if (SHIFT) {
+        it.t0 = itt * g.wt + g.st;      // rolled: frames t0 + dt taken modulo T in win_row
+        axis_segment(ih, g.wh, g.sh, g.G, &it.h0, &it.eh);
+        axis_segment(iw, g.ww, g.sw, g.G, &it.w0, &it.ew);
+        it.S = g.wt * it.eh * it.ew;
+    } else {
+        it.t0 = itt * g.wt;
+        it.h0 = ih * g.wh;
+        it.w0 = iw * g.ww;
+        it.eh = g.wh, it.ew = g.ww, it.S = g.S;
+    }
     return it;
 }
 
-// row, within the clip, of token i of the window
+// row, within the clip, of token i of the box
+template <bool SHIFT>
 __device__ __forceinline__ int win_row(const WinGeom& g, const WinItem& it, int i) {
-    const int hw = g.wh * g.ww;
-    const int dt = i / hw, r = i - dt * hw, dh = r / g.ww, dw = r - dh * g.ww;
-    return (it.t0 + dt) * g.P + 1 + (it.h0 + dh) * g.G + it.w0 + dw;
+    const int hw = it.eh * it.ew;
+    const int dt = i / hw, r = i - dt * hw, dh = r / it.ew, dw = r - dh * it.ew;
+    int f = it.t0 + dt;
+    if (SHIFT && f >= g.T) f -= g.T;      // f <= (T - wt + st) + wt - 1 < 2 T: one subtraction is the modulo
+    return f * g.P + 1 + (it.h0 + dh) * g.G + it.w0 + dw;
 }
 
 // index into the [B T, H, P] statistics of clip row r
@@ -72,6 +100,7 @@ __device__ __forceinline__ long long stat_index(const WinGeom& g, const WinItem&
 }
 
 // gather the 64 streamed tokens i0 .. i0 + 63 of the window into two swizzled 8 KiB images (rows past S: zeros)
+template <bool SHIFT>
 __device__ __forceinline__ void stage_pair(__amdgpu_buffer_rsrc_t ra, int lda2, AIM_LDS char* ia, __amdgpu_buffer_rsrc_t rb, int ldb2,
                                            AIM_LDS char* ib, const WinGeom& g, const WinItem& it, int i0, int wave, int nwaves,
                                            int lane) {
@@ -79,8 +108,8 @@ __device__ __forceinline__ void stage_pair(__amdgpu_buffer_rsrc_t ra, int lda2, 
     for (int p = wave; p < 8; p += nwaves) {
         const int i = i0 + p * 8 + srow;
         unsigned va = AIM_OOB, vb = AIM_OOB;
-        if (i < g.S) {
-            const int r = win_row(g, it, i);
+        if (i < it.S) {
+            const int r = win_row<SHIFT>(g, it, i);
             va = (unsigned)(r * lda2 + schunk * 16);
             vb = (unsigned)(r * ldb2 + schunk * 16);
         }
@@ -150,19 +179,21 @@ __device__ __forceinline__ void load_frag(bf16x8 (&f)[2], const bf16_t* row, int
     __shared__ __attribute__((aligned(16))) char smem_raw[2 * 8192];                           \
     AIM_LDS char* sA = (AIM_LDS char*)smem_raw;                                                \
     AIM_LDS char* sB = sA + 8192;                                                              \
-    const WinItem it = win_item(g, (int)blockIdx.x);                                           \
+    const WinItem it = win_item<SHIFT>(g, (int)blockIdx.x);                                    \
     const int tid = threadIdx.x, lane = tid & 63;                                              \
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), nwaves = (int)(blockDim.x >> 6); \
+    if (SHIFT && (int)blockIdx.y * nwaves * 16 >= it.S) return; /* a small box: before any barrier */ \
     const int frow = lane & 15, fq = lane >> 4;                                                \
     const int D = g.H * 64, ld = 3 * D;                                                        \
     const long long clip_rows = (long long)g.T * g.P;                                          \
     const int own0 = ((int)blockIdx.y * nwaves + wave) * 16;                                   \
-    const bool active = own0 < g.S;                                                            \
+    const bool active = own0 < it.S;                                                           \
     const int oi = own0 + frow;                                                                \
-    const bool own_ok = oi < g.S;                                                              \
-    const int orow = win_row(g, it, own_ok ? oi : g.S - 1);                                    \
-    const int ntiles = (g.S + 63) >> 6;
+    const bool own_ok = oi < it.S;                                                             \
+    const int orow = win_row<SHIFT>(g, it, own_ok ? oi : it.S - 1);                            \
+    const int ntiles = (it.S + 63) >> 6;
 
+template <bool SHIFT>
 __global__ __launch_bounds__(512) void win_attn_fwd_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
                                                            float* __restrict__ lse, const WinGeom g) {
     WIN_PROLOGUE
@@ -177,18 +208,18 @@ __global__ __launch_bounds__(512) void win_attn_fwd_kernel(const bf16_t* __restr
     for (int dt = 0; dt < 4; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int kt = 0; kt < ntiles; ++kt) {
         if (kt) __syncthreads();
-        stage_pair(rK, ld * 2, sA, rV, ld * 2, sB, g, it, kt * 64, wave, nwaves, lane);
+        stage_pair<SHIFT>(rK, ld * 2, sA, rV, ld * 2, sB, g, it, kt * 64, wave, nwaves, lane);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (!active) continue;
         f32x4 s[4];
         tile_scores(s, sA, qf, frow, fq);
-        if (kt == ntiles - 1 && (g.S & 63)) {
+        if (kt == ntiles - 1 && (it.S & 63)) {
 #pragma unroll
             for (int t = 0; t < 4; ++t)
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
-                    if (kt * 64 + t * 16 + fq * 4 + e >= g.S) s[t][e] = -INFINITY;
+                    if (kt * 64 + t * 16 + fq * 4 + e >= it.S) s[t][e] = -INFINITY;
         }
         float mx = m;
 #pragma unroll
@@ -221,6 +252,7 @@ __global__ __launch_bounds__(512) void win_attn_fwd_kernel(const bf16_t* __restr
 }
 
 // own = queries: delta and dQ
+template <bool SHIFT>
 __global__ __launch_bounds__(512) void win_attn_dq_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ out,
                                                           const bf16_t* __restrict__ dout, const float* __restrict__ lse,
                                                           float* __restrict__ delta, bf16_t* __restrict__ dqkv, const WinGeom g) {
@@ -250,20 +282,20 @@ __global__ __launch_bounds__(512) void win_attn_dq_kernel(const bf16_t* __restri
     for (int dt = 0; dt < 4; ++dt) acc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int kt = 0; kt < ntiles; ++kt) {
         if (kt) __syncthreads();
-        stage_pair(rK, ld * 2, sA, rV, ld * 2, sB, g, it, kt * 64, wave, nwaves, lane);
+        stage_pair<SHIFT>(rK, ld * 2, sA, rV, ld * 2, sB, g, it, kt * 64, wave, nwaves, lane);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (!active) continue;
         f32x4 s[4], dp[4];
         tile_scores(s, sA, qf, frow, fq);
         tile_scores(dp, sB, dof, frow, fq);
-        const bool tail = kt == ntiles - 1 && (g.S & 63);
+        const bool tail = kt == ntiles - 1 && (it.S & 63);
 #pragma unroll
         for (int t = 0; t < 4; ++t)
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 float p = __builtin_amdgcn_exp2f(s[t][e] * C2 - lse2);
-                if (tail && kt * 64 + t * 16 + fq * 4 + e >= g.S) p = 0.f;
+                if (tail && kt * 64 + t * 16 + fq * 4 + e >= it.S) p = 0.f;
                 s[t][e] = p * (dp[t][e] - dl) * 0.125f;
             }
         tile_accum(acc, sA, s, frow, fq);
@@ -273,6 +305,7 @@ __global__ __launch_bounds__(512) void win_attn_dq_kernel(const bf16_t* __restri
 }
 
 // own = keys: dK and dV
+template <bool SHIFT>
 __global__ __launch_bounds__(512) void win_attn_dkv_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dout,
                                                            const float* __restrict__ lse, const float* __restrict__ delta,
                                                            bf16_t* __restrict__ dqkv, const WinGeom g) {
@@ -291,12 +324,12 @@ __global__ __launch_bounds__(512) void win_attn_dkv_kernel(const bf16_t* __restr
     for (int dt = 0; dt < 4; ++dt) dk[dt] = dv[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int qt = 0; qt < ntiles; ++qt) {
         if (qt) __syncthreads();
-        stage_pair(rQ, ld * 2, sA, rO, D * 2, sB, g, it, qt * 64, wave, nwaves, lane);
+        stage_pair<SHIFT>(rQ, ld * 2, sA, rO, D * 2, sB, g, it, qt * 64, wave, nwaves, lane);
         if (tid < 64) {      // a streamed query past S: lse = +inf makes its probability 2^-inf = 0
             const int i = qt * 64 + tid;
             float a = INFINITY, d = 0.f;
-            if (i < g.S) {
-                const long long si = stat_index(g, it, win_row(g, it, i));
+            if (i < it.S) {
+                const long long si = stat_index(g, it, win_row<SHIFT>(g, it, i));
                 a = lse[si] * LOG2E;
                 d = delta[si];
             }
@@ -329,7 +362,8 @@ __global__ __launch_bounds__(512) void win_attn_dkv_kernel(const bf16_t* __restr
 }
 
 // argument checks shared by both entry points; fills the geometry, the grid and the block size
-int win_geom(const char* who, WinGeom* g, dim3* grid, int* threads, int B, int T, int N, int P, int H, int wt, int wh, int ww) {
+int win_geom(const char* who, WinGeom* g, dim3* grid, int* threads, int B, int T, int N, int P, int H, int wt, int wh, int ww,
+             int st = 0, int sh = 0, int sw = 0) {
     AIM_CHECK_ARG(B > 0 && T > 0 && N > 1 && P >= N && H > 0 && wt > 0 && wh > 0 && ww > 0,
                   "%s: unsupported shape B=%d T=%d N=%d P=%d H=%d window=(%d,%d,%d)", who, B, T, N, P, H, wt, wh, ww);
     int G = 1;
@@ -344,12 +378,20 @@ int win_geom(const char* who, WinGeom* g, dim3* grid, int* threads, int B, int T
     AIM_CHECK_ARG(S <= WIN_MAX_S, "%s: %lld tokens per window, at most %d", who, S, WIN_MAX_S);
     AIM_CHECK_ARG((long long)T * P * 3 * 64 * H * 2 < 0x7fffffffLL, "%s: a clip's qkv rows span more than 2 GiB (T=%d P=%d H=%d)",
                   who, T, P, H);
-    const long long items = (long long)B * (T / wt) * (G / wh) * (G / ww) * H;
+    AIM_CHECK_ARG(st >= 0 && sh >= 0 && sw >= 0 && st < wt && sh < wh && sw < ww,
+                  "%s: shift (%d,%d,%d) outside [0, window) of the clipped window (%d,%d,%d)", who, st, sh, sw, wt, wh, ww);
+    AIM_CHECK_ARG(!(st && wt == T) && !(sh && wh == G) && !(sw && ww == G),
+                  "%s: shift (%d,%d,%d) on an axis whose window (%d,%d,%d) spans the grid (%d,%d,%d)", who, st, sh, sw, wt, wh, ww,
+                  T, G, G);
+    // a shifted h / w axis is cut at 0, s, s + w, ...: one segment more than windows
+    const int nh = G / wh + (sh ? 1 : 0), nw = G / ww + (sw ? 1 : 0);
+    const long long items = (long long)B * (T / wt) * nh * nw * H;
     AIM_CHECK_ARG(items < 0x7fffffffLL, "%s: %lld (window, head) items", who, items);
     g->T = T, g->P = P, g->G = G, g->H = H;
     g->wt = wt, g->wh = wh, g->ww = ww;
-    g->nh = G / wh, g->nw = G / ww, g->nW = (T / wt) * g->nh * g->nw;
+    g->nh = nh, g->nw = nw, g->nW = (T / wt) * nh * nw;
     g->S = (int)S;
+    g->st = st, g->sh = sh, g->sw = sw;
     const int nwaves = S <= 16 ? 1 : S <= 32 ? 2 : S <= 64 ? 4 : 8;
     *threads = nwaves * 64;
     *grid = dim3((unsigned)items, (unsigned)((S + nwaves * 16 - 1) / (nwaves * 16)));
@@ -365,7 +407,7 @@ extern "C" int aim_win_attn_fwd(const aim_bf16* qkv, aim_bf16* out, float* lse, 
     int threads;
     if (int rc = win_geom("win_attn_fwd", &g, &grid, &threads, B, T, N, P, H, wt, wh, ww)) return rc;
     AIM_CHECK_ARG(qkv && out && lse, "win_attn_fwd: null pointer");
-    hipLaunchKernelGGL(win_attn_fwd_kernel, grid, dim3(threads), 0, (hipStream_t)stream, (const bf16_t*)qkv, (bf16_t*)out, lse, g);
+    hipLaunchKernelGGL(win_attn_fwd_kernel<false>, grid, dim3(threads), 0, (hipStream_t)stream, (const bf16_t*)qkv, (bf16_t*)out, lse, g);
     AIM_CHECK_LAUNCH("aim_win_attn_fwd");
     return 0;
 }
@@ -378,11 +420,52 @@ extern "C" int aim_win_attn_bwd(const aim_bf16* qkv, const aim_bf16* out, const 
     if (int rc = win_geom("win_attn_bwd", &g, &grid, &threads, B, T, N, P, H, wt, wh, ww)) return rc;
     AIM_CHECK_ARG(qkv && out && dout && lse && delta && dqkv, "win_attn_bwd: null pointer");
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(win_attn_dq_kernel, grid, dim3(threads), 0, st, (const bf16_t*)qkv, (const bf16_t*)out, (const bf16_t*)dout,
+    hipLaunchKernelGGL(win_attn_dq_kernel<false>, grid, dim3(threads), 0, st, (const bf16_t*)qkv, (const bf16_t*)out, (const bf16_t*)dout,
                        lse, delta, (bf16_t*)dqkv, g);
     AIM_CHECK_LAUNCH("aim_win_attn_bwd(dq)");
-    hipLaunchKernelGGL(win_attn_dkv_kernel, grid, dim3(threads), 0, st, (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta,
+    hipLaunchKernelGGL(win_attn_dkv_kernel<false>, grid, dim3(threads), 0, st, (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta,
                        (bf16_t*)dqkv, g);
     AIM_CHECK_LAUNCH("aim_win_attn_bwd(dkv)");
+    return 0;
+}
+
+// Shifted windows (AIM_FLASH's odd blocks, vitclip_aim_flash.py: roll by -shift, strips along the border, attention inside each
+// strip, nine cats, roll back).  In ORIGINAL coordinates that is, each axis on its own:
+//   h, w with shift s > 0: [0, G) cut at 0, s, s + w, s + 2 w, ..., G -- a first segment of s, whole windows, a last segment of
+//     w - s.  Nothing wraps: the rolled strips [-w:-s] and [-s:] ARE the last and the first segment.
+//   t: whole windows in rolled coordinates; window k holds the frames (k wt + st + dt) mod T.  The last one wraps.
+// One sequence = one (t window, h segment, w segment) box, tokens in (dt, dh, dw) row-major order; the boxes partition the patch
+// tokens and the t map is a bijection on the clip's frames, so every result row still has one writer.  The boxes differ in
+// size: gridDim.y is sized by the largest (a whole window) and a workgroup past its own box's S leaves before its first
+// barrier; the tile loop runs to the box's own S.  With st = sh = sw = 0 the items, the token order and the tile order are
+// those of the unshifted kernels, hence their bits.
+extern "C" int aim_win_attn_fwd_shift(const aim_bf16* qkv, aim_bf16* out, float* lse, int B, int T, int N, int P, int H, int wt,
+                                      int wh, int ww, int st, int sh, int sw, void* stream) {
+    WinGeom g;
+    dim3 grid;
+    int threads;
+    if (int rc = win_geom("win_attn_fwd_shift", &g, &grid, &threads, B, T, N, P, H, wt, wh, ww, st, sh, sw)) return rc;
+    AIM_CHECK_ARG(qkv && out && lse, "win_attn_fwd_shift: null pointer");
+    hipLaunchKernelGGL(win_attn_fwd_kernel<true>, grid, dim3(threads), 0, (hipStream_t)stream, (const bf16_t*)qkv, (bf16_t*)out, lse,
+                       g);
+    AIM_CHECK_LAUNCH("aim_win_attn_fwd_shift");
+    return 0;
+}
+
+extern "C" int aim_win_attn_bwd_shift(const aim_bf16* qkv, const aim_bf16* out, const aim_bf16* dout, const float* lse,
+                                      float* delta, aim_bf16* dqkv, int B, int T, int N, int P, int H, int wt, int wh, int ww,
+                                      int st, int sh, int sw, void* stream) {
+    WinGeom g;
+    dim3 grid;
+    int threads;
+    if (int rc = win_geom("win_attn_bwd_shift", &g, &grid, &threads, B, T, N, P, H, wt, wh, ww, st, sh, sw)) return rc;
+    AIM_CHECK_ARG(qkv && out && dout && lse && delta && dqkv, "win_attn_bwd_shift: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(win_attn_dq_kernel<true>, grid, dim3(threads), 0, s, (const bf16_t*)qkv, (const bf16_t*)out,
+                       (const bf16_t*)dout, lse, delta, (bf16_t*)dqkv, g);
+    AIM_CHECK_LAUNCH("aim_win_attn_bwd_shift(dq)");
+    hipLaunchKernelGGL(win_attn_dkv_kernel<true>, grid, dim3(threads), 0, s, (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta,
+                       (bf16_t*)dqkv, g);
+    AIM_CHECK_LAUNCH("aim_win_attn_bwd_shift(dkv)");
     return 0;
 }

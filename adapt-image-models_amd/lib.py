@@ -64,6 +64,8 @@ SIGNATURES = {
     "aim_attn_bwd_shift": [P, P, P, P, P, P, I, I, I, I, I, POINTER(c_int), P],
     "aim_win_attn_fwd": [P, P, P, I, I, I, I, I, I, I, I, P],
     "aim_win_attn_bwd": [P, P, P, P, P, P, I, I, I, I, I, I, I, I, P],
+    "aim_win_attn_fwd_shift": [P, P, P, I, I, I, I, I, I, I, I, I, I, I, P],
+    "aim_win_attn_bwd_shift": [P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, P],
     "aim_cls_attn_fwd": [P, P, P, I, I, I, I, P],
     "aim_cls_attn_bwd": [P, P, P, P, I, I, I, I, I, P],
     "aim_tattn_fwd": [P, P, P, I, I, I, I, P],
@@ -111,7 +113,7 @@ SIGNATURES = {
     "aim_layernorm_gb_bwd": [P, I, L, P, L, P, P, P, P, I, I, P, L, P],
 }
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 
 def load_library():

@@ -141,6 +141,8 @@ def register_into_mmaction() -> bool:
     MB.register_module(name="AIM", force=True, module=AIM)       # stock AIM (vitclip_aim.py:353), wind_attn=False
     from .aim_flash_win import AIM_FLASH_WIN
     MB.register_module(name="AIM_FLASH_WIN", force=True, module=AIM_FLASH_WIN)     # vitclip_aim_flash_win.py:276, wind_attn=True
+    from .aim_flash import AIM_FLASH
+    MB.register_module(name="AIM_FLASH", force=True, module=AIM_FLASH)             # vitclip_aim_flash.py:402, wind_attn=True
     return True
 
 

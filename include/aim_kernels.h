@@ -32,7 +32,7 @@ extern "C" {
 
 typedef uint16_t aim_bf16;
 
-#define AIM_ABI_VERSION 11
+#define AIM_ABI_VERSION 12
 
 int aim_version(void);                /* == AIM_ABI_VERSION */
 const char* aim_last_error(void);     /* message of the last failing call on this thread */
@@ -247,6 +247,27 @@ int aim_win_attn_fwd(const aim_bf16* qkv, aim_bf16* out, float* lse, int B, int 
                      int ww, void* stream);
 int aim_win_attn_bwd(const aim_bf16* qkv, const aim_bf16* out, const aim_bf16* dout, const float* lse, float* delta,
                      aim_bf16* dqkv, int B, int T, int N, int P, int H, int wt, int wh, int ww, void* stream);
+
+/* Shifted-window form (ABI 12; AIM_FLASH's odd blocks, vitclip_aim_flash.py: roll by -shift, border strips, attention inside
+ * each strip, stitch, roll back).  Buffers, layouts and guarantees are those of aim_win_attn_fwd / aim_win_attn_bwd; only the
+ * grouping of the patch tokens into sequences differs.  With (wt, wh, ww) the clipped extents and (st, sh, sw) the shifts, in
+ * ORIGINAL (unrolled) coordinates and each axis on its own:
+ *   h (w alike), sh > 0: [0, G) is cut at 0, sh, sh + wh, sh + 2*wh, ..., G: a first segment of sh rows, whole windows, a last
+ *     segment of wh - sh.  Nothing wraps.  sh = 0: the windows [ih*wh, (ih+1)*wh).
+ *   t: whole windows in rolled coordinates; window k holds the frames (k*wt + st + dt) mod T, dt = 0 .. wt-1, of its own clip.
+ * One sequence is one (t window, h segment, w segment) box with its tokens in (dt, dh, dw) row-major order; attention is
+ * plain softmax self-attention inside the box, and every patch token lies in exactly one box.  The boxes and the t wrap are
+ * addresses inside the kernels: no rolled or strip-ordered copy of anything exists, and all (box, head) items of every size
+ * run in one launch (three for bwd).
+ * Bit-for-bit: st = sh = sw = 0 gives the bits of aim_win_attn_fwd / aim_win_attn_bwd; sh = sw = 0, st > 0 gives the bits of
+ * those entries on buffers whose frames were rolled by -st inside each clip, rolled back by +st.
+ * Refused before any launch: a shift < 0 or >= its clipped extent, a non-zero shift on an axis whose clipped extent equals
+ * the grid's, and everything aim_win_attn_* refuses. */
+int aim_win_attn_fwd_shift(const aim_bf16* qkv, aim_bf16* out, float* lse, int B, int T, int N, int P, int H, int wt, int wh,
+                           int ww, int st, int sh, int sw, void* stream);
+int aim_win_attn_bwd_shift(const aim_bf16* qkv, const aim_bf16* out, const aim_bf16* dout, const float* lse, float* delta,
+                           aim_bf16* dqkv, int B, int T, int N, int P, int H, int wt, int wh, int ww, int st, int sh, int sw,
+                           void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Temporal attention over the T class tokens of each clip -- vit_clip.py:220-224 with

@@ -1,9 +1,9 @@
 """Whole training steps (forward + backward + FlatAdamW) of the AIM_FLASH_WIN recipes' model on one GPU, for DESIGN.md 2e.
 
-    python tools/flash_win_step.py [--clips 16] [--frames 16] [--window 16,7,7] [--steps 4] [--warmup 2] [--rounds 3] [--json OUT]
+    python tools/flash_win_step.py [--clips 16] [--frames 16] [--window 16,7,7] [--steps 4] [--warmup 2] [--rounds 3] [--shift] [--json OUT]
 
 The model is the hmdb51 recipe's (ViT-B/16, drop_path_rate 0.2, adapter_scale 0.5, prompt, 51 classes; its 16 frames unless
---frames says otherwise) with pretrained=None and non-zero D_fc2.  Under `rocprofv3 --kernel-trace --stats -- python
+--frames says otherwise) with pretrained=None and non-zero D_fc2; --shift builds the AIM_FLASH recipes' model instead.  Under `rocprofv3 --kernel-trace --stats -- python
 tools/flash_win_step.py --rounds 1` the per-kernel table gives the window attention's share of the step
 (tools/prof_summary.py)."""
 import argparse
@@ -25,6 +25,7 @@ def main():
     ap.add_argument("--steps", type=int, default=4)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--shift", action="store_true", help="AIM_FLASH: every odd block on windows shifted by half a window")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     import aim_amd
@@ -32,9 +33,9 @@ def main():
     dev = torch.device("cuda")
     window = tuple(int(v) for v in a.window.split(","))
     cfg = dict(type='Recognizer3D',
-               backbone=dict(type='AIM_FLASH_WIN', input_resolution=224, patch_size=16, width=768, layers=12, heads=12,
+               backbone=dict(type='AIM_FLASH' if a.shift else 'AIM_FLASH_WIN', input_resolution=224, patch_size=16, width=768, layers=12, heads=12,
                              num_frames=a.frames, drop_path_rate=0.2, adapter_scale=0.5, pretrained=None, use_flash_attn=True,
-                             checkpoint=False, prompt=True, wind_attn=True, window_size=window, not_shift=True),
+                             checkpoint=False, prompt=True, wind_attn=True, window_size=window, not_shift=not a.shift),
                cls_head=dict(type='I3DHead', in_channels=768, num_classes=51, spatial_type='avg', dropout_ratio=0.5),
                test_cfg=dict(average_clips='prob'))
     torch.manual_seed(0)
@@ -67,7 +68,7 @@ def main():
         loss = run(a.steps)
         torch.cuda.synchronize()
         times.append((time.perf_counter() - t0) * 1e3 / a.steps)
-    res = dict(clips=a.clips, frames=a.frames, window=list(window), rows=a.clips * a.frames * 197, ms_per_step=sorted(times),
+    res = dict(backbone=type(m.backbone).__name__, clips=a.clips, frames=a.frames, window=list(window), rows=a.clips * a.frames * 197, ms_per_step=sorted(times),
                median_ms=sorted(times)[len(times) // 2], peak_GB=torch.cuda.max_memory_allocated() / 1e9,
                last_loss=float(loss.detach()))
     print(json.dumps(res), flush=True)
