@@ -24,9 +24,10 @@
 // summation order (the tile order), each pass holds 32 / 64 accumulator VGPRs and 16 KiB of LDS, and the price is computing
 // s and dP twice (5 MFMA products against 3.5 per pass pair: 7 against 5).  Every patch token lies in exactly one window.
 //
-// The kernels are templates on SHIFT: false is the window partition above, true the box partition of shifted windows (AIM_FLASH's
-// odd blocks; the rule stands above the *_shift entry points at the end of the file).  Only win_item, win_row and the early exit
-// of a workgroup past a small box differ.
+// The kernels are templates on MODE: WIN_PLAIN is the window partition above, WIN_WRAP the box partition of shifted windows whose
+// t windows wrap round the clip (AIM_FLASH's odd blocks; the rule stands above the *_shift entry points at the end of the file),
+// WIN_CUT the one in which t is cut like h and w (AIM's odd blocks; above the *_cut entry points).  Only win_item, win_row and
+// the early exit of a workgroup past a small box differ.
 //
 // Tails: streamed rows past S are zero-filled by the buffer bounds check (AIM_OOB) and their probabilities forced to 0; own
 // tokens past S load the window's last token and are not stored.
@@ -38,20 +39,22 @@ namespace {
 constexpr int WIN_MAX_S = AIM_WIN_ATTN_MAX_S;
 constexpr float LOG2E = 1.4426950408889634f;
 constexpr float C2 = 0.125f * LOG2E;      // 1/sqrt(dh) * log2(e): the softmax runs in base 2
+constexpr int WIN_PLAIN = 0, WIN_WRAP = 1, WIN_CUT = 2;
 
 struct WinGeom {
     int T, P, G, H;       // P: tokens per frame of the buffers (row stride); the grid's tokens are 1 .. G G
     int wt, wh, ww;       // window extents (after clipping)
-    int nh, nw, nW;       // boxes along h and w, boxes per clip
+    int nh, nw, nW;       // boxes along h and w, boxes per clip (nW = boxes along t * nh * nw)
     int S;                // tokens of a whole window (the largest box)
     int st, sh, sw;       // shifts (the *_shift entries; 0 otherwise)
 };
 
-// One sequence: the box [t0, t0 + wt) x [h0, h0 + eh) x [w0, w0 + ew) of the grid, S = wt eh ew tokens in (dt, dh, dw) row-major
-// order.  Unshifted: every box is a window (eh = wh, ew = ww, S = g.S).  Shifted: the rule above the *_shift entry points.
+// One sequence: the box [t0, t0 + et) x [h0, h0 + eh) x [w0, w0 + ew) of the grid, S = et eh ew tokens in (dt, dh, dw) row-major
+// order.  Unshifted: every box is a window (et = wt, eh = wh, ew = ww, S = g.S).  Shifted: the rule above the *_shift entry
+// points (et = wt) or above the *_cut ones.
 struct WinItem {
     int b, h, t0, h0, w0;
-    int eh, ew, S;
+    int et, eh, ew, S;
 };
 
 // segment j of an axis of extent w cut at 0, s, s + w, s + 2 w, ...: its start and its length (s = 0: j w and w)
@@ -62,34 +65,39 @@ __device__ __forceinline__ void axis_segment(int j, int w, int s, int G, int* st
     *len = s ? e - a : w;
 }
 
-template <bool SHIFT>
+template <int MODE>
 __device__ __forceinline__ WinItem win_item(const WinGeom& g, int item) {
     WinItem it;
     it.h = item % g.H;
     const int bw = item / g.H, win = bw % g.nW;
     it.b = bw / g.nW;
     const int iw = win % g.nw, r = win / g.nw, ih = r % g.nh, itt = r / g.nh;
-    if (SHIFT) {
-        it.t0 = itt * g.wt + g.st;      // rolled: frames t0 + dt taken modulo T in win_row
-        axis_segment(ih, g.wh, g.sh, g.G, &it.h0, &it.eh);
-        axis_segment(iw, g.ww, g.sw, g.G, &it.w0, &it.ew);
-        it.S = g.wt * it.eh * it.ew;
-    } else {
+    if (MODE == WIN_PLAIN) {
         it.t0 = itt * g.wt;
         it.h0 = ih * g.wh;
         it.w0 = iw * g.ww;
-        it.eh = g.wh, it.ew = g.ww, it.S = g.S;
+        it.et = g.wt, it.eh = g.wh, it.ew = g.ww, it.S = g.S;
+    } else {
+        if (MODE == WIN_WRAP) {
+            it.t0 = itt * g.wt + g.st;      // rolled: frames t0 + dt taken modulo T in win_row
+            it.et = g.wt;
+        } else {
+            axis_segment(itt, g.wt, g.st, g.T, &it.t0, &it.et);      // t0 + et <= T: no frame index is taken modulo T
+        }
+        axis_segment(ih, g.wh, g.sh, g.G, &it.h0, &it.eh);
+        axis_segment(iw, g.ww, g.sw, g.G, &it.w0, &it.ew);
+        it.S = it.et * it.eh * it.ew;
     }
     return it;
 }
 
 // row, within the clip, of token i of the box
-template <bool SHIFT>
+template <int MODE>
 __device__ __forceinline__ int win_row(const WinGeom& g, const WinItem& it, int i) {
     const int hw = it.eh * it.ew;
     const int dt = i / hw, r = i - dt * hw, dh = r / it.ew, dw = r - dh * it.ew;
     int f = it.t0 + dt;
-    if (SHIFT && f >= g.T) f -= g.T;      // f <= (T - wt + st) + wt - 1 < 2 T: one subtraction is the modulo
+    if (MODE == WIN_WRAP && f >= g.T) f -= g.T;      // f <= (T - wt + st) + wt - 1 < 2 T: one subtraction is the modulo
     return f * g.P + 1 + (it.h0 + dh) * g.G + it.w0 + dw;
 }
 
@@ -100,7 +108,7 @@ __device__ __forceinline__ long long stat_index(const WinGeom& g, const WinItem&
 }
 
 // gather the 64 streamed tokens i0 .. i0 + 63 of the window into two swizzled 8 KiB images (rows past S: zeros)
-template <bool SHIFT>
+template <int MODE>
 __device__ __forceinline__ void stage_pair(__amdgpu_buffer_rsrc_t ra, int lda2, AIM_LDS char* ia, __amdgpu_buffer_rsrc_t rb, int ldb2,
                                            AIM_LDS char* ib, const WinGeom& g, const WinItem& it, int i0, int wave, int nwaves,
                                            int lane) {
@@ -109,7 +117,7 @@ __device__ __forceinline__ void stage_pair(__amdgpu_buffer_rsrc_t ra, int lda2, 
         const int i = i0 + p * 8 + srow;
         unsigned va = AIM_OOB, vb = AIM_OOB;
         if (i < it.S) {
-            const int r = win_row<SHIFT>(g, it, i);
+            const int r = win_row<MODE>(g, it, i);
             va = (unsigned)(r * lda2 + schunk * 16);
             vb = (unsigned)(r * ldb2 + schunk * 16);
         }
@@ -179,10 +187,10 @@ __device__ __forceinline__ void load_frag(bf16x8 (&f)[2], const bf16_t* row, int
     __shared__ __attribute__((aligned(16))) char smem_raw[2 * 8192];                           \
     AIM_LDS char* sA = (AIM_LDS char*)smem_raw;                                                \
     AIM_LDS char* sB = sA + 8192;                                                              \
-    const WinItem it = win_item<SHIFT>(g, (int)blockIdx.x);                                    \
+    const WinItem it = win_item<MODE>(g, (int)blockIdx.x);                                    \
     const int tid = threadIdx.x, lane = tid & 63;                                              \
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), nwaves = (int)(blockDim.x >> 6); \
-    if (SHIFT && (int)blockIdx.y * nwaves * 16 >= it.S) return; /* a small box: before any barrier */ \
+    if (MODE != WIN_PLAIN && (int)blockIdx.y * nwaves * 16 >= it.S) return; /* a small box: before any barrier */ \
     const int frow = lane & 15, fq = lane >> 4;                                                \
     const int D = g.H * 64, ld = 3 * D;                                                        \
     const long long clip_rows = (long long)g.T * g.P;                                          \
@@ -190,10 +198,10 @@ __device__ __forceinline__ void load_frag(bf16x8 (&f)[2], const bf16_t* row, int
     const bool active = own0 < it.S;                                                           \
     const int oi = own0 + frow;                                                                \
     const bool own_ok = oi < it.S;                                                             \
-    const int orow = win_row<SHIFT>(g, it, own_ok ? oi : it.S - 1);                            \
+    const int orow = win_row<MODE>(g, it, own_ok ? oi : it.S - 1);                            \
     const int ntiles = (it.S + 63) >> 6;
 
-template <bool SHIFT>
+template <int MODE>
 __global__ __launch_bounds__(512) void win_attn_fwd_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
                                                            float* __restrict__ lse, const WinGeom g) {
     WIN_PROLOGUE
@@ -208,7 +216,7 @@ __global__ __launch_bounds__(512) void win_attn_fwd_kernel(const bf16_t* __restr
     for (int dt = 0; dt < 4; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int kt = 0; kt < ntiles; ++kt) {
         if (kt) __syncthreads();
-        stage_pair<SHIFT>(rK, ld * 2, sA, rV, ld * 2, sB, g, it, kt * 64, wave, nwaves, lane);
+        stage_pair<MODE>(rK, ld * 2, sA, rV, ld * 2, sB, g, it, kt * 64, wave, nwaves, lane);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (!active) continue;
@@ -252,7 +260,7 @@ __global__ __launch_bounds__(512) void win_attn_fwd_kernel(const bf16_t* __restr
 }
 
 // own = queries: delta and dQ
-template <bool SHIFT>
+template <int MODE>
 __global__ __launch_bounds__(512) void win_attn_dq_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ out,
                                                           const bf16_t* __restrict__ dout, const float* __restrict__ lse,
                                                           float* __restrict__ delta, bf16_t* __restrict__ dqkv, const WinGeom g) {
@@ -282,7 +290,7 @@ __global__ __launch_bounds__(512) void win_attn_dq_kernel(const bf16_t* __restri
     for (int dt = 0; dt < 4; ++dt) acc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int kt = 0; kt < ntiles; ++kt) {
         if (kt) __syncthreads();
-        stage_pair<SHIFT>(rK, ld * 2, sA, rV, ld * 2, sB, g, it, kt * 64, wave, nwaves, lane);
+        stage_pair<MODE>(rK, ld * 2, sA, rV, ld * 2, sB, g, it, kt * 64, wave, nwaves, lane);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (!active) continue;
@@ -305,7 +313,7 @@ __global__ __launch_bounds__(512) void win_attn_dq_kernel(const bf16_t* __restri
 }
 
 // own = keys: dK and dV
-template <bool SHIFT>
+template <int MODE>
 __global__ __launch_bounds__(512) void win_attn_dkv_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dout,
                                                            const float* __restrict__ lse, const float* __restrict__ delta,
                                                            bf16_t* __restrict__ dqkv, const WinGeom g) {
@@ -324,12 +332,12 @@ __global__ __launch_bounds__(512) void win_attn_dkv_kernel(const bf16_t* __restr
     for (int dt = 0; dt < 4; ++dt) dk[dt] = dv[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int qt = 0; qt < ntiles; ++qt) {
         if (qt) __syncthreads();
-        stage_pair<SHIFT>(rQ, ld * 2, sA, rO, D * 2, sB, g, it, qt * 64, wave, nwaves, lane);
+        stage_pair<MODE>(rQ, ld * 2, sA, rO, D * 2, sB, g, it, qt * 64, wave, nwaves, lane);
         if (tid < 64) {      // a streamed query past S: lse = +inf makes its probability 2^-inf = 0
             const int i = qt * 64 + tid;
             float a = INFINITY, d = 0.f;
             if (i < it.S) {
-                const long long si = stat_index(g, it, win_row<SHIFT>(g, it, i));
+                const long long si = stat_index(g, it, win_row<MODE>(g, it, i));
                 a = lse[si] * LOG2E;
                 d = delta[si];
             }
@@ -363,7 +371,7 @@ __global__ __launch_bounds__(512) void win_attn_dkv_kernel(const bf16_t* __restr
 
 // argument checks shared by both entry points; fills the geometry, the grid and the block size
 int win_geom(const char* who, WinGeom* g, dim3* grid, int* threads, int B, int T, int N, int P, int H, int wt, int wh, int ww,
-             int st = 0, int sh = 0, int sw = 0) {
+             int st = 0, int sh = 0, int sw = 0, bool cut_t = false) {
     AIM_CHECK_ARG(B > 0 && T > 0 && N > 1 && P >= N && H > 0 && wt > 0 && wh > 0 && ww > 0,
                   "%s: unsupported shape B=%d T=%d N=%d P=%d H=%d window=(%d,%d,%d)", who, B, T, N, P, H, wt, wh, ww);
     int G = 1;
@@ -383,13 +391,13 @@ int win_geom(const char* who, WinGeom* g, dim3* grid, int* threads, int B, int T
     AIM_CHECK_ARG(!(st && wt == T) && !(sh && wh == G) && !(sw && ww == G),
                   "%s: shift (%d,%d,%d) on an axis whose window (%d,%d,%d) spans the grid (%d,%d,%d)", who, st, sh, sw, wt, wh, ww,
                   T, G, G);
-    // a shifted h / w axis is cut at 0, s, s + w, ...: one segment more than windows
-    const int nh = G / wh + (sh ? 1 : 0), nw = G / ww + (sw ? 1 : 0);
-    const long long items = (long long)B * (T / wt) * nh * nw * H;
+    // a shifted h / w axis is cut at 0, s, s + w, ...: one segment more than windows; so is t where it is cut and not rolled
+    const int nh = G / wh + (sh ? 1 : 0), nw = G / ww + (sw ? 1 : 0), nt = T / wt + (cut_t && st ? 1 : 0);
+    const long long items = (long long)B * nt * nh * nw * H;
     AIM_CHECK_ARG(items < 0x7fffffffLL, "%s: %lld (window, head) items", who, items);
     g->T = T, g->P = P, g->G = G, g->H = H;
     g->wt = wt, g->wh = wh, g->ww = ww;
-    g->nh = nh, g->nw = nw, g->nW = (T / wt) * nh * nw;
+    g->nh = nh, g->nw = nw, g->nW = nt * nh * nw;
     g->S = (int)S;
     g->st = st, g->sh = sh, g->sw = sw;
     const int nwaves = S <= 16 ? 1 : S <= 32 ? 2 : S <= 64 ? 4 : 8;
@@ -407,7 +415,7 @@ extern "C" int aim_win_attn_fwd(const aim_bf16* qkv, aim_bf16* out, float* lse, 
     int threads;
     if (int rc = win_geom("win_attn_fwd", &g, &grid, &threads, B, T, N, P, H, wt, wh, ww)) return rc;
     AIM_CHECK_ARG(qkv && out && lse, "win_attn_fwd: null pointer");
-    hipLaunchKernelGGL(win_attn_fwd_kernel<false>, grid, dim3(threads), 0, (hipStream_t)stream, (const bf16_t*)qkv, (bf16_t*)out, lse, g);
+    hipLaunchKernelGGL(win_attn_fwd_kernel<WIN_PLAIN>, grid, dim3(threads), 0, (hipStream_t)stream, (const bf16_t*)qkv, (bf16_t*)out, lse, g);
     AIM_CHECK_LAUNCH("aim_win_attn_fwd");
     return 0;
 }
@@ -420,10 +428,10 @@ extern "C" int aim_win_attn_bwd(const aim_bf16* qkv, const aim_bf16* out, const 
     if (int rc = win_geom("win_attn_bwd", &g, &grid, &threads, B, T, N, P, H, wt, wh, ww)) return rc;
     AIM_CHECK_ARG(qkv && out && dout && lse && delta && dqkv, "win_attn_bwd: null pointer");
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(win_attn_dq_kernel<false>, grid, dim3(threads), 0, st, (const bf16_t*)qkv, (const bf16_t*)out, (const bf16_t*)dout,
+    hipLaunchKernelGGL(win_attn_dq_kernel<WIN_PLAIN>, grid, dim3(threads), 0, st, (const bf16_t*)qkv, (const bf16_t*)out, (const bf16_t*)dout,
                        lse, delta, (bf16_t*)dqkv, g);
     AIM_CHECK_LAUNCH("aim_win_attn_bwd(dq)");
-    hipLaunchKernelGGL(win_attn_dkv_kernel<false>, grid, dim3(threads), 0, st, (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta,
+    hipLaunchKernelGGL(win_attn_dkv_kernel<WIN_PLAIN>, grid, dim3(threads), 0, st, (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta,
                        (bf16_t*)dqkv, g);
     AIM_CHECK_LAUNCH("aim_win_attn_bwd(dkv)");
     return 0;
@@ -446,7 +454,7 @@ extern "C" int aim_win_attn_fwd_shift(const aim_bf16* qkv, aim_bf16* out, float*
     int threads;
     if (int rc = win_geom("win_attn_fwd_shift", &g, &grid, &threads, B, T, N, P, H, wt, wh, ww, st, sh, sw)) return rc;
     AIM_CHECK_ARG(qkv && out && lse, "win_attn_fwd_shift: null pointer");
-    hipLaunchKernelGGL(win_attn_fwd_kernel<true>, grid, dim3(threads), 0, (hipStream_t)stream, (const bf16_t*)qkv, (bf16_t*)out, lse,
+    hipLaunchKernelGGL(win_attn_fwd_kernel<WIN_WRAP>, grid, dim3(threads), 0, (hipStream_t)stream, (const bf16_t*)qkv, (bf16_t*)out, lse,
                        g);
     AIM_CHECK_LAUNCH("aim_win_attn_fwd_shift");
     return 0;
@@ -461,11 +469,50 @@ extern "C" int aim_win_attn_bwd_shift(const aim_bf16* qkv, const aim_bf16* out, 
     if (int rc = win_geom("win_attn_bwd_shift", &g, &grid, &threads, B, T, N, P, H, wt, wh, ww, st, sh, sw)) return rc;
     AIM_CHECK_ARG(qkv && out && dout && lse && delta && dqkv, "win_attn_bwd_shift: null pointer");
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(win_attn_dq_kernel<true>, grid, dim3(threads), 0, s, (const bf16_t*)qkv, (const bf16_t*)out,
+    hipLaunchKernelGGL(win_attn_dq_kernel<WIN_WRAP>, grid, dim3(threads), 0, s, (const bf16_t*)qkv, (const bf16_t*)out,
                        (const bf16_t*)dout, lse, delta, (bf16_t*)dqkv, g);
     AIM_CHECK_LAUNCH("aim_win_attn_bwd_shift(dq)");
-    hipLaunchKernelGGL(win_attn_dkv_kernel<true>, grid, dim3(threads), 0, s, (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta,
+    hipLaunchKernelGGL(win_attn_dkv_kernel<WIN_WRAP>, grid, dim3(threads), 0, s, (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta,
                        (bf16_t*)dqkv, g);
     AIM_CHECK_LAUNCH("aim_win_attn_bwd_shift(dkv)");
+    return 0;
+}
+
+// Cut windows (AIM's odd blocks, vitclip_aim.py: roll by -shift, attention inside whole windows of the rolled grid under an
+// additive -100 mask between the regions compute_mask numbers, roll back).  The regions of an axis are [0, T - w), [T - w, T - s),
+// [T - s, T) in rolled coordinates, so a rolled window that holds the wrap point falls into the pieces on either side of it.  In
+// ORIGINAL coordinates EVERY axis, t included, is therefore cut at 0, s, s + w, s + 2 w, ..., extent: a first segment of s, whole
+// windows, a last segment of w - s; an axis with s = 0 keeps plain windows.  One sequence = one (t segment, h segment, w segment)
+// box, (T / wt + (st > 0)) nh nw of them per clip, with plain softmax attention inside (a weight of exactly 0 where the reference
+// leaves at most (S - 1) e^(spread - 100)).  Everything else is the *_shift entries': arguments, buffers, refusals, one writer per row.
+// With st = 0 the items, the token order and the tile order are those of *_shift at the same (sh, sw), hence their bits.
+extern "C" int aim_win_attn_fwd_cut(const aim_bf16* qkv, aim_bf16* out, float* lse, int B, int T, int N, int P, int H, int wt,
+                                    int wh, int ww, int st, int sh, int sw, void* stream) {
+    WinGeom g;
+    dim3 grid;
+    int threads;
+    if (int rc = win_geom("win_attn_fwd_cut", &g, &grid, &threads, B, T, N, P, H, wt, wh, ww, st, sh, sw, true)) return rc;
+    AIM_CHECK_ARG(qkv && out && lse, "win_attn_fwd_cut: null pointer");
+    hipLaunchKernelGGL(win_attn_fwd_kernel<WIN_CUT>, grid, dim3(threads), 0, (hipStream_t)stream, (const bf16_t*)qkv, (bf16_t*)out, lse,
+                       g);
+    AIM_CHECK_LAUNCH("aim_win_attn_fwd_cut");
+    return 0;
+}
+
+extern "C" int aim_win_attn_bwd_cut(const aim_bf16* qkv, const aim_bf16* out, const aim_bf16* dout, const float* lse, float* delta,
+                                    aim_bf16* dqkv, int B, int T, int N, int P, int H, int wt, int wh, int ww, int st, int sh,
+                                    int sw, void* stream) {
+    WinGeom g;
+    dim3 grid;
+    int threads;
+    if (int rc = win_geom("win_attn_bwd_cut", &g, &grid, &threads, B, T, N, P, H, wt, wh, ww, st, sh, sw, true)) return rc;
+    AIM_CHECK_ARG(qkv && out && dout && lse && delta && dqkv, "win_attn_bwd_cut: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(win_attn_dq_kernel<WIN_CUT>, grid, dim3(threads), 0, s, (const bf16_t*)qkv, (const bf16_t*)out,
+                       (const bf16_t*)dout, lse, delta, (bf16_t*)dqkv, g);
+    AIM_CHECK_LAUNCH("aim_win_attn_bwd_cut(dq)");
+    hipLaunchKernelGGL(win_attn_dkv_kernel<WIN_CUT>, grid, dim3(threads), 0, s, (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta,
+                       (bf16_t*)dqkv, g);
+    AIM_CHECK_LAUNCH("aim_win_attn_bwd_cut(dkv)");
     return 0;
 }

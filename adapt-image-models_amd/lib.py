@@ -66,6 +66,8 @@ SIGNATURES = {
     "aim_win_attn_bwd": [P, P, P, P, P, P, I, I, I, I, I, I, I, I, P],
     "aim_win_attn_fwd_shift": [P, P, P, I, I, I, I, I, I, I, I, I, I, I, P],
     "aim_win_attn_bwd_shift": [P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, P],
+    "aim_win_attn_fwd_cut": [P, P, P, I, I, I, I, I, I, I, I, I, I, I, P],
+    "aim_win_attn_bwd_cut": [P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, P],
     "aim_cls_attn_fwd": [P, P, P, I, I, I, I, P],
     "aim_cls_attn_bwd": [P, P, P, P, I, I, I, I, I, P],
     "aim_tattn_fwd": [P, P, P, I, I, I, I, P],
@@ -113,7 +115,7 @@ SIGNATURES = {
     "aim_layernorm_gb_bwd": [P, I, L, P, L, P, P, P, P, I, I, P, L, P],
 }
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 
 def load_library():

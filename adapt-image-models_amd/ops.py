@@ -373,6 +373,29 @@ def win_attn_bwd_shift(qkv, out, dout, lse, delta, dqkv, B, T, N, H, window, shi
           "aim_win_attn_bwd_shift")
 
 
+def win_attn_fwd_cut(qkv, out, lse, B, T, N, H, window, shift, P=None):
+    """win_attn_fwd_shift with the t axis cut like h and w, at 0, st, st + wt, ..., T, instead of wrapping round the clip's end
+    (AIM's masked shifted windows; include/aim_kernels.h).  st = 0 gives win_attn_fwd_shift's bits."""
+    _chk(qkv, BF16, "qkv"); _chk(out, BF16, "out"); _chk(lse, F32, "lse")
+    wt, wh, ww = (int(w) for w in window)
+    st, sh, sw = (int(s) for s in shift)
+    check(load_library().aim_win_attn_fwd_cut(qkv.data_ptr(), out.data_ptr(), lse.data_ptr(), B, T, N, N if P is None else P, H,
+                                              wt, wh, ww, st, sh, sw, _stream()),
+          "aim_win_attn_fwd_cut")
+
+
+def win_attn_bwd_cut(qkv, out, dout, lse, delta, dqkv, B, T, N, H, window, shift, P=None):
+    """backward of win_attn_fwd_cut: writes the patch rows of dqkv [B*T*P, 3D] and of delta [B*T, H, P]."""
+    _chk(qkv, BF16, "qkv"); _chk(out, BF16, "out"); _chk(dout, BF16, "dout"); _chk(dqkv, BF16, "dqkv")
+    _chk(lse, F32, "lse"); _chk(delta, F32, "delta")
+    wt, wh, ww = (int(w) for w in window)
+    st, sh, sw = (int(s) for s in shift)
+    check(load_library().aim_win_attn_bwd_cut(qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(), delta.data_ptr(),
+                                              dqkv.data_ptr(), B, T, N, N if P is None else P, H, wt, wh, ww, st, sh, sw,
+                                              _stream()),
+          "aim_win_attn_bwd_cut")
+
+
 def attn_fwd_cls(qkv, out_cls, lse_cls, BT, N, H):
     """attn_fwd for the class query of every (frame, head) alone: out_cls [BT, D], lse_cls [BT, H]."""
     _chk(qkv, BF16, "qkv"); _chk(out_cls, BF16, "out_cls"); _chk(lse_cls, F32, "lse_cls")

@@ -32,7 +32,7 @@ extern "C" {
 
 typedef uint16_t aim_bf16;
 
-#define AIM_ABI_VERSION 12
+#define AIM_ABI_VERSION 13
 
 int aim_version(void);                /* == AIM_ABI_VERSION */
 const char* aim_last_error(void);     /* message of the last failing call on this thread */
@@ -268,6 +268,22 @@ int aim_win_attn_fwd_shift(const aim_bf16* qkv, aim_bf16* out, float* lse, int B
 int aim_win_attn_bwd_shift(const aim_bf16* qkv, const aim_bf16* out, const aim_bf16* dout, const float* lse, float* delta,
                            aim_bf16* dqkv, int B, int T, int N, int P, int H, int wt, int wh, int ww, int st, int sh, int sw,
                            void* stream);
+
+/* Cut-window form (ABI 13; AIM's odd blocks, vitclip_aim.py:62-75 and :180-187: roll by -shift, whole windows of the rolled grid
+ * under an additive -100 mask between compute_mask's regions, roll back).  Arguments, buffers, layouts, guarantees and refusals
+ * are those of the *_shift entries; only the t axis is grouped differently: it is cut like h and w, at 0, st, st + wt, st + 2*wt,
+ * ..., T (st = 0: the windows [it*wt, (it+1)*wt)), and no frame index is taken modulo T.  One sequence is one (t segment, h
+ * segment, w segment) box, (T/wt + (st > 0)) * nh * nw of them per clip, tokens in (dt, dh, dw) row-major order, plain softmax
+ * self-attention inside it; every patch token lies in exactly one box.  A pair of tokens the reference's mask separates gets a
+ * weight of exactly 0 here, where the reference leaves at most (S - 1) e^(spread - 100) of probability mass (spread: the largest logit
+ * difference inside a window).
+ * Bit-for-bit: st = 0 gives the bits of aim_win_attn_fwd_shift / aim_win_attn_bwd_shift at the same (sh, sw), so the all-zero
+ * shift gives those of aim_win_attn_fwd / aim_win_attn_bwd. */
+int aim_win_attn_fwd_cut(const aim_bf16* qkv, aim_bf16* out, float* lse, int B, int T, int N, int P, int H, int wt, int wh,
+                         int ww, int st, int sh, int sw, void* stream);
+int aim_win_attn_bwd_cut(const aim_bf16* qkv, const aim_bf16* out, const aim_bf16* dout, const float* lse, float* delta,
+                         aim_bf16* dqkv, int B, int T, int N, int P, int H, int wt, int wh, int ww, int st, int sh, int sw,
+                         void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Temporal attention over the T class tokens of each clip -- vit_clip.py:220-224 with
