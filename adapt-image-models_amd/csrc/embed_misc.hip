@@ -597,30 +597,39 @@ __global__ __launch_bounds__(256) void cast_multi_kernel(const aim_cast_desc* __
 }
 
 // AdamW (decoupled weight decay) on flat fp32 buffers, torch.optim.AdamW semantics.
+// One element's update.  The four-wide body and the n % 4 tail both run THIS function, with its three fused multiply-adds
+// spelled out and no other contraction allowed: the compiler contracts the two loops differently when left to choose, and an
+// element's result must not depend on where it sits in the flat buffer.  c = 1 - lr wd (one fma), a = lr / bc1.
+__device__ __forceinline__ void adamw_elem(float& p, float g, float& m, float& v, float c, float a, float b1, float omb1,
+                                           float b2, float omb2, float bc2s, float eps) {
+#pragma clang fp contract(off)
+    m = __builtin_fmaf(omb1, g, b1 * m);
+    v = __builtin_fmaf(b2, v, omb2 * g * g);
+    p = __builtin_fmaf(c, p, -(a * m / (sqrtf(v) / bc2s + eps)));
+}
+
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                     float* __restrict__ m, float* __restrict__ v, long long n, float lr,
                                                     float b1, float b2, float eps, float wd, float bc1, float bc2s, float gs) {
     const long long i = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
     if (i >= n) return;
+    const float c = __builtin_fmaf(-lr, wd, 1.0f), a = lr / bc1, omb1 = 1.0f - b1, omb2 = 1.0f - b2;
     if (i + 3 < n) {
         f32x4 pp = *(f32x4*)(p + i), mm = *(f32x4*)(m + i), vv = *(f32x4*)(v + i);
         const f32x4 gg = *(const f32x4*)(g + i) * gs;       // gs = 1 / world: the SUM all-reduce becomes the mean here
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            pp[e] *= 1.0f - lr * wd;
-            mm[e] = b1 * mm[e] + (1.0f - b1) * gg[e];
-            vv[e] = b2 * vv[e] + (1.0f - b2) * gg[e] * gg[e];
-            pp[e] -= (lr / bc1) * mm[e] / (sqrtf(vv[e]) / bc2s + eps);
+            float pe = pp[e], me = mm[e], ve = vv[e];
+            adamw_elem(pe, gg[e], me, ve, c, a, b1, omb1, b2, omb2, bc2s, eps);
+            pp[e] = pe; mm[e] = me; vv[e] = ve;
         }
         *(f32x4*)(p + i) = pp;
         *(f32x4*)(m + i) = mm;
         *(f32x4*)(v + i) = vv;
     } else {
         for (long long j = i; j < n; ++j) {
-            float pp = p[j] * (1.0f - lr * wd);
-            const float gj = g[j] * gs;
-            const float mm = b1 * m[j] + (1.0f - b1) * gj, vv = b2 * v[j] + (1.0f - b2) * gj * gj;
-            pp -= (lr / bc1) * mm / (sqrtf(vv) / bc2s + eps);
+            float pp = p[j], mm = m[j], vv = v[j];
+            adamw_elem(pp, g[j] * gs, mm, vv, c, a, b1, omb1, b2, omb2, bc2s, eps);
             p[j] = pp; m[j] = mm; v[j] = vv;
         }
     }
@@ -631,6 +640,8 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
 extern "C" int aim_adamw_flat(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1,
                               float beta2, float eps, float weight_decay, int step, float grad_scale, void* stream) {
     AIM_CHECK_ARG(p && g && m && v && n > 0 && step >= 1, "adamw: bad arguments");
+    AIM_CHECK_ARG((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0,
+                  "adamw: p, g, m and v must be 16-byte aligned");
     const float bc1 = 1.0f - powf(beta1, (float)step), bc2s = sqrtf(1.0f - powf(beta2, (float)step));
     hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
                        (long long)n, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale);

@@ -178,15 +178,17 @@ __global__ __launch_bounds__(256) void ce_soft_finish_kernel(const float* __rest
     }
 }
 
-// dW[c][d] += sum_b dscore[b][c] pooled[b][d]; db[c] += sum_b dscore[b][c]   (grid: C blocks; fixed summation order)
+// dW[c][d] += sum_b dscore[b][c] pooled[b][d]; db[c] += sum_b dscore[b][c]   (grid: C blocks; fixed summation order; either
+// output may be NULL)
 __global__ __launch_bounds__(256) void head_wgrad_kernel(const float* __restrict__ dscore, const float* __restrict__ pooled,
                                                          float* __restrict__ dW, float* __restrict__ db, int B, int D, int C) {
     const int c = blockIdx.x, tid = threadIdx.x;
-    for (int d = tid; d < D; d += 256) {
-        float acc = 0.f;
-        for (int b = 0; b < B; ++b) acc += dscore[(long long)b * C + c] * pooled[(long long)b * D + d];
-        dW[(long long)c * D + d] += acc;
-    }
+    if (dW)
+        for (int d = tid; d < D; d += 256) {
+            float acc = 0.f;
+            for (int b = 0; b < B; ++b) acc += dscore[(long long)b * C + c] * pooled[(long long)b * D + d];
+            dW[(long long)c * D + d] += acc;
+        }
     if (tid == 0 && db) {
         float acc = 0.f;
         for (int b = 0; b < B; ++b) acc += dscore[(long long)b * C + c];
@@ -232,9 +234,10 @@ extern "C" int aim_head_fwd(const float* feat, const float* drop, const float* W
 extern "C" int aim_head_bwd(const float* dscore, const float* pooled, const float* drop, const float* W, float* dW,
                             float* db, float* dfeat, int B, int T, int D, int C, void* stream) {
     AIM_CHECK_ARG(dscore && pooled && W && B > 0 && T > 0 && D > 0 && C > 0, "head_bwd: bad arguments");
+    AIM_CHECK_ARG(dW || db || dfeat, "head_bwd: no output requested (dW, db and dfeat are all NULL)");
     AIM_CHECK_ARG((size_t)(C + 256) * 4 <= 64 * 1024, "head_bwd: C=%d too large", C);
     hipStream_t st = (hipStream_t)stream;
-    if (dW) {
+    if (dW || db) {
         hipLaunchKernelGGL(head_wgrad_kernel, dim3(C), dim3(256), 0, st, dscore, pooled, dW, db, B, D, C);
         AIM_CHECK_LAUNCH("aim_head_bwd(wgrad)");
     }

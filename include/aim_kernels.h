@@ -402,7 +402,8 @@ int aim_cast_multi(const aim_cast_desc* table_dev, int n, void* stream);
  * Optimizer boundary: AdamW (torch.optim.AdamW semantics, decoupled decay) on ONE flat fp32 buffer
  * per parameter group -- the reference steps 149 small tensors through mmcv's optimizer hook
  * (mmaction/utils/optimizer.py:22-33, configs/recognition/vit/vitclip_base_k400.py:96-102).
- * `step` is the 1-based update count (bias correction).  Pointers 16-byte aligned.
+ * `step` is the 1-based update count (bias correction).  p, g, m and v must be 16-byte aligned (the kernel moves four
+ * floats at a time): a misaligned pointer is refused.
  * `grad_scale` multiplies g on the fly: 1 / world_size turns the SUM all-reduce of the flat gradient buffer into
  * DDP's mean (mmaction/apis/train.py:106-110) without a separate pass over the buffer.
  * ------------------------------------------------------------------------------------------ */
@@ -416,6 +417,7 @@ int aim_adamw_flat(float* p, const float* g, float* m, float* v, int64_t n, floa
  *              caller-drawn factor table drop[B, D] (0 or 1/(1-p); NULL = eval), fc_cls:
  *              pooled[b][d] = drop[b][d] * mean_t feat[b][t][d]  (saved for backward) ; score = pooled W^T + bias.
  *   head_bwd : dW[C, D] += dscore^T pooled ; db[C] += colsum(dscore) ; dfeat[b][t][d] = drop[b][d]/T * (dscore W)[b][d].
+ *              dW, db and dfeat are each optional (NULL: not computed, the others unchanged); all three NULL is refused.
  *   ce_topk  : CrossEntropyLoss hard-label path (mmaction/models/losses/cross_entropy_loss.py:78) + top-k accuracy
  *              (mmaction/core/evaluation/accuracy.py:90-109, numpy argsort tie order: a label is in the top k iff
  *              fewer than k classes score higher or tie with a larger index), all on the device:
