@@ -10,7 +10,8 @@ along h and along w into the strips ``[-w:-s]`` and ``[-s:]``, runs attention in
 with nine ``cat``s and a second roll.  In the ORIGINAL coordinates that is a partition of the grid into boxes: the h and w
 axes are cut at 0, s, s + w, s + 2 w, ... (nothing wraps: the rolled strips are the axis' last and first segment), the t axis
 keeps whole windows that start at st and wrap round the clip's end.  ``aim_win_attn_fwd_shift`` / ``aim_win_attn_bwd_shift``
-take that rule as addresses, so the block is ``aim_flash_win._block_forward`` with one more argument and no rolled,
+take that rule as addresses, so the block is ``aim_flash_win._block_forward`` with one more argument (which goes to
+``win_block.win_temporal_forward``, where steps 1-3 live) and no rolled,
 strip-ordered or stitched copy of anything exists.
 
 Block i is shifted when ``i % 2 == 1 and not not_shift``, by ``window_size[k] // 2``, zeroed on every axis where the grid does
@@ -20,11 +21,7 @@ cannot run a geometry in which some shift is non-zero while the h or the w shift
 """
 from .aim_flash_win import AIM_FLASH_WIN
 from .registry import BACKBONES
-
-
-def clip_shift(window_size, T: int, G: int):
-    """the shift of the reference's ``get_window_size`` (:51-64): half a window, 0 where the grid does not exceed the window"""
-    return tuple(0 if x <= int(w) else int(w) // 2 for w, x in zip(window_size, (T, G, G)))
+from .win_block import clip_shift
 
 
 def check_shift(shift, window_size, T: int, G: int):

@@ -29,6 +29,9 @@ into it (B T rows), steps 5 and 6 run on all P rows, and the slot's value after 
 it.  Its gradient row is extracted and zeroed once ln_1's backward of step 5 has produced it.  The window kernel takes the
 row stride P beside N, so the slot costs no copy of the other rows; only the embedding is copied into the P layout once.
 
+Steps 1-3, the out-projection of 4, their backward and the slot layout are plain functions in win_block.py, shared with the
+windowed ``AIM`` (aim_variant.py); steps 4-6 are this file's.
+
 The reference's shifted branch (``not_shift=False``) rolls the windows back and then DISCARDS the result (``:188`` assigns
 ``windows_attn``, ``:192`` rearranges ``shifted_win``): its output is mis-aligned by the shift.  It is not built.
 """
@@ -44,13 +47,10 @@ from .backbone import (_AUX_GRAD, _DP_RESERVE, BF16, F32, Adapter, LayerNorm, Qu
                        _embed_forward, _empty, _Fork, _Frozen, _GradBufs, _ln_post_backward, _ln_post_forward,
                        _mlp_adapter_backward, _mlp_adapter_forward, _wgrads_beside)
 from .registry import BACKBONES
+from .win_block import (check_win_clip, check_window, clip_window, from_slot_layout, to_slot_layout, win_prompt_grad,
+                        win_temporal_backward, win_temporal_forward)
 
 _LOG = logging.getLogger("aim_amd")
-
-
-def clip_window(window_size, T: int, G: int):
-    """the reference's ``get_window_size`` (:51-64): an extent that reaches the grid's is clipped to it"""
-    return tuple(min(int(w), x) for w, x in zip(window_size, (T, G, G)))
 
 
 class _MHA(nn.Module):
@@ -115,28 +115,9 @@ def _block_forward(x, fz: _Frozen, adp: Dict[str, _AdapterW], B, T, N, P, H, win
     BT, r = B * T, fz.r
     prompt = P != N
     xv = lambda t: t.view(BT, P, -1)
-    # ---- 1: ln_1 and the QKV projection over every row
-    xl = _empty((M, D), BF16, dev)
-    mean1, rstd1 = _empty((M,), F32, dev), _empty((M,), F32, dev)
-    ops.layernorm_fwd(x, fz.g1, fz.b1, M, D, D, y_bf16=xl, mean=mean1, rstd=rstd1)
-    qkv = _empty((M, 3 * D), BF16, dev)
-    ops.gemm(xl, fz.Wqkv, ops.EPI_BF16, qkv, bias=fz.bqkv)
-    del xl
-    # ---- 2, 3: window attention on the patch rows, class-token attention on the class rows, into one [M, D] buffer
-    at_ = _empty((M, D), BF16, dev)
-    lse_w = _empty((BT, H, P), F32, dev)
-    if shift is None:
-        ops.win_attn_fwd(qkv, at_, lse_w, B, T, N, H, window, P=P)
-    else:
-        ops.win_attn_fwd_shift(qkv, at_, lse_w, B, T, N, H, window, shift, P=P)
-    ot, probs = _empty((BT, D), BF16, dev), _empty((B, H, T, T), F32, dev)
-    ops.cls_attn_fwd(qkv, ot, probs, B, T, P, H)
-    xv(at_)[:, 0] = ot
-    if prompt:
-        xv(at_)[:, N] = 0
-    # ---- 4: out_proj, T_Adapter, x1 = x + f1 (GELU(ta W1^T + b1) W2^T + b2)
-    ta = _empty((M, D), BF16, dev)
-    ops.gemm(at_, fz.Wo, ops.EPI_BF16, ta, bias=fz.bo)
+    # ---- 1, 2, 3 and out_proj (win_block.py)
+    ta, c = win_temporal_forward(x, fz, B, T, N, P, H, window, shift, False)
+    # ---- 4: T_Adapter, x1 = x + f1 (GELU(ta W1^T + b1) W2^T + b2)
     tad = adp["T_Adapter"]
     t_pre, t_hs = _empty((M, r), BF16, dev), _empty((M, r), BF16, dev)
     ops.gemm(ta, tad.W1, ops.EPI_ACT, t_hs, bias=tad.b1, out2=t_pre, act=ops.ACT_GELU, af=f1, ntok=P, aux_grad=_AUX_GRAD)
@@ -168,9 +149,9 @@ def _block_forward(x, fz: _Frozen, adp: Dict[str, _AdapterW], B, T, N, P, H, win
     x3, xn, mean2, rstd2, hcat_pre, a_s = _mlp_adapter_forward(x2, fz, tokm, P, save, af=f3)
     if not save:
         return x3, None
-    c = dict(x=x, mean1=mean1, rstd1=rstd1, qkv=qkv, at=at_, lse_w=lse_w, probs=probs, ta=ta, t_pre=t_pre, t_hs=t_hs, x1=x1,
-             mean1b=mean1b, rstd1b=rstd1b, qkv2=qkv2, ao=ao, lse=lse, xb=xb, s_pre=s_pre, s_h=s_h, x2=x2, mean2=mean2,
-             rstd2=rstd2, xn=xn, hcat_pre=hcat_pre, a_s=a_s, f1=f1, f2=f2, f3=f3, tokm=tokm)
+    c.update(x=x, ta=ta, t_pre=t_pre, t_hs=t_hs, x1=x1, mean1b=mean1b, rstd1b=rstd1b, qkv2=qkv2, ao=ao, lse=lse, xb=xb,
+             s_pre=s_pre, s_h=s_h, x2=x2, mean2=mean2, rstd2=rstd2, xn=xn, hcat_pre=hcat_pre, a_s=a_s, f1=f1, f2=f2, f3=f3,
+             tokm=tokm)
     return x3, c
 
 
@@ -181,8 +162,6 @@ def _block_backward(dyb, c, fz: _Frozen, adp: Dict[str, _AdapterW], grads, B, T,
     dev = dyb.device
     M, D = dyb.shape
     BT, r = B * T, fz.r
-    prompt = P != N
-    xv = lambda t: t.view(BT, P, -1)
     fork = _Fork(dev, "bwd")
     f1, f2, f3 = c["f1"], c["f2"], c["f3"]
     dx2b, later = _mlp_adapter_backward(dyb, c["x2"], c["mean2"], c["rstd2"], c["xn"], c["hcat_pre"], c["a_s"], c["tokm"], fz,
@@ -210,10 +189,7 @@ def _block_backward(dyb, c, fz: _Frozen, adp: Dict[str, _AdapterW], grads, B, T,
     dx1b = _empty((M, D), BF16, dev)
     ops.layernorm_bwd(dxl, c["x1"], fz.g1, c["mean1b"], c["rstd1b"], M, D, lddy=D, ldx=D, lddx=D, dres=dres, dx_bf16=dx1b)
     del dres
-    dprompt = None
-    if prompt:          # the slot's row IS d(prompt) = one more gradient of ta's class rows; nothing else flows through the slot
-        dprompt = xv(dx1b)[:, N].to(F32, copy=True).contiguous()
-        xv(dx1b)[:, N] = 0
+    dprompt = win_prompt_grad(dx1b, BT, N, P)
     # ---- 4: x1 = x + t_hs W2^T + f1 b2,  t_hs = f1 GELU(ta W1^T + b1),  ta = [cls_attn | windows_attn] Wo^T + bo
     tad, gt = adp["T_Adapter"], grads["T_Adapter"]
     t_hs, ta = c["t_hs"], c["ta"]
@@ -222,29 +198,9 @@ def _block_backward(dyb, c, fz: _Frozen, adp: Dict[str, _AdapterW], grads, B, T,
     ops.gemm(dx1b, tad.W2T, ops.EPI_DACT, dtp, aux=c["t_pre"], act=ops.ACT_GELU, af=f1, ntok=P, aux_grad=_AUX_GRAD)
     dta = _empty((M, D), BF16, dev)
     ops.gemm(dtp, tad.W1T, ops.EPI_BF16, dta)
-    if prompt:
-        ops.add_rows(dta, P * D, dprompt)             # class rows: row 0 of every frame
-    dat = _empty((M, D), BF16, dev)
-    ops.gemm(dta, fz.WoT, ops.EPI_BF16, dat, reserve_cus=_DP_RESERVE)
-    del dta
-    # ---- 2, 3: the two attentions write disjoint rows of d(qkv): the window kernel the patch rows, cls_attn_bwd ADDS into
-    # the class rows (zeroed first, with the slot's)
-    xv(dqkv)[:, 0] = 0
-    if prompt:
-        xv(dqkv)[:, N] = 0
-    if shift is None:
-        ops.win_attn_bwd(c["qkv"], c["at"], dat, c["lse_w"], delta, dqkv, B, T, N, H, window, P=P)
-    else:
-        ops.win_attn_bwd_shift(c["qkv"], c["at"], dat, c["lse_w"], delta, dqkv, B, T, N, H, window, shift, P=P)
-    ops.cls_attn_bwd(c["qkv"], c["probs"], xv(dat)[:, 0].contiguous(), dqkv, B, T, P, H)
-    del dat
     later.append(lambda: ops.wgrad(dtp, ta, gt["D_fc1.weight"], gt["D_fc1.bias"]))
-    ops.gemm(dqkv, fz.WqkvT, ops.EPI_BF16, dxl, reserve_cus=_DP_RESERVE)
-    del dqkv
-    dxb = _empty((M, D), BF16, dev)
-    ops.layernorm_bwd(dxl, c["x"], fz.g1, c["mean1"], c["rstd1"], M, D, lddy=D, ldx=D, lddx=D, dres=dx1b, dx_bf16=dxb)
-    if prompt:
-        xv(dxb)[:, N] = 0
+    # ---- out_proj, 3, 2, 1 (win_block.py), on the spatial step's d(qkv), delta and dxl buffers
+    dxb = win_temporal_backward(dta, dx1b, c, fz, dqkv, delta, dxl, B, T, N, P, H, window, shift, False, dprompt)
     _wgrads_beside(fork, later, keep)
     return dxb
 
@@ -267,12 +223,7 @@ class _FlashWinFn(torch.autograd.Function):
         frozen = model._frozen_operands()
         adp = model._stage_adapters(frozen, params)
         tok, x0, mean0, rstd0, tmp = _embed_forward(model, frozen, imgs, temporal)
-        if P != N:          # once per forward: into the P-row layout (row N = the prompt's slot, zero until block 0 fills it)
-            x = _empty((BT * P, D), F32, dev)
-            x.view(BT, P, D)[:, :N] = x0.view(BT, N, D)
-            x.view(BT, P, D)[:, N] = 0
-        else:
-            x = x0
+        x = to_slot_layout(x0, BT, N, P)
         del x0
         if model.inference_precision == 'fp8' and not need_grad and not model._fp8_warned:
             model._fp8_warned = True
@@ -314,8 +265,7 @@ class _FlashWinFn(torch.autograd.Function):
                                   s["window"], keep, s["shifts"][i])
             s["ctxs"][i] = None
             gbufs.layer_ready(i)
-        if P != N:          # once per backward: back to the embedding's N tokens per frame (the slot's row is zero)
-            dxb = dxb.view(BT, P, D)[:, :N].contiguous().view(BT * N, D)
+        dxb = from_slot_layout(dxb, BT, N, P)
         grads = _embed_backward(gbufs, frozen, s, dxb, keep, B, T, N, D)
         ctx.saved = None
         return grads
@@ -339,13 +289,7 @@ class AIM_FLASH_WIN(ViT_CLIP):
             raise NotImplementedError("AIM_FLASH_WIN(num_tadapter=2) (T_Adapter_in) is not built")
         if checkpoint:
             raise NotImplementedError("AIM_FLASH_WIN(checkpoint=True) (activation recompute per block) is not built")
-        G = input_resolution // patch_size
-        win = clip_window(window_size, num_frames, G)
-        if len(tuple(window_size)) != 3 or any(w <= 0 for w in win) or num_frames % win[0] or G % win[1] or G % win[2]:
-            raise ValueError(f"window_size={tuple(window_size)} (clipped to {win}) does not divide the {num_frames} x {G} x {G} grid")
-        if win[0] * win[1] * win[2] > ops.WIN_ATTN_MAX_S:
-            raise ValueError(f"{win[0] * win[1] * win[2]} tokens per window: the window attention kernels take at most "
-                             f"{ops.WIN_ATTN_MAX_S}")
+        check_window(window_size, num_frames, input_resolution // patch_size)
         super().__init__(input_resolution, num_frames, patch_size, width, 0, heads, drop_path_rate,
                          adapter_scale=adapter_scale, pretrained=pretrained)
         self.layers = layers
@@ -421,10 +365,7 @@ class AIM_FLASH_WIN(ViT_CLIP):
     def forward(self, x: torch.Tensor):
         blend = self._take_blend_check_clip(x, "AIM_FLASH_WIN")
         T, N = x.shape[2], (x.shape[3] // self.patch_size) ** 2 + 1
-        if N + int(self.prompt) > 288:
-            raise ValueError(f"{N + int(self.prompt)} tokens per frame: the spatial attention kernels take at most 288")
-        if T > 32:
-            raise ValueError(f"{T} frames: the class-token attention kernels take at most 32")
+        check_win_clip(T, N, self.prompt)
         x = self._arm_clip(x, blend)
         y = _FlashWinFn.apply(self, torch.is_grad_enabled(), x, *self._trainable_list())     # [B, D, T]
         return y.unsqueeze(-1).unsqueeze(-1)

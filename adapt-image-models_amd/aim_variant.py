@@ -33,6 +33,9 @@ draws over the N token positions,
 
 The prompt lives as in aim_flash_win.py: the residual stream keeps P = N + 1 rows per frame, the extra row is a slot BEHIND
 the frame's tokens, filled in step 5, dead after step 6, and its gradient row returns through the class rows of ``ta``.
+
+Steps 1-3, the out-projection of 4 and the slot layout are win_block.py's, shared with aim_flash_win.py; T_Adapter under the
+first DropPath and the spatial step are ``_t_adapter_*`` and ``_spatial_*`` below, shared by the stock and the windowed block.
 """
 import logging
 from typing import Dict, List, Optional
@@ -40,50 +43,54 @@ from typing import Dict, List, Optional
 import torch
 
 from . import ops
-from .aim_flash import clip_shift
-from .aim_flash_win import clip_window
 from .backbone import (BF16, F32, ViT_CLIP, _AdapterW, _embed_backward, _embed_forward, _empty, _Fork, _Frozen, _GradBufs,
                        _ln_post_backward, _ln_post_forward, _mlp_adapter_backward, _mlp_adapter_forward, _wgrads_beside)
 from .registry import BACKBONES
+from .win_block import (check_win_clip, check_window, clip_shift, clip_window, from_slot_layout, to_slot_layout, win_prompt_grad,
+                        win_temporal_backward, win_temporal_forward)
 
 _LOG = logging.getLogger("aim_amd")
 
 
-def aim_block_forward(x, fz: _Frozen, adp: Dict[str, _AdapterW], B, T, N, H, dp1, dms2, save: bool):
-    """x: [B*T*N, D] f32 frame-major -> x3.  ``dp1``: the first DropPath factor per token (no adapter scale,
-    vitclip_aim.py:205); ``dms2``: the second one times ``scale`` (:210)."""
-    dev = x.device
+def _t_adapter_forward(ta, x, tad: _AdapterW, dp1, ntok, r):
+    """x1 = x + dp1[token] T_Adapter(ta) (no adapter scale, no skip) -> t_pre, t_hs, x1.  The DropPath factor is folded into
+    the stored activation (t_hs = dp1 * GELU(pre)), so the D_fc2 weight gradient is a plain product and the bias rides along
+    token-scaled as `vec`."""
     M, D = x.shape
-    BT, r = B * T, fz.r
-    tad, sad = adp["T_Adapter"], adp["S_Adapter"]
-    # ---- temporal adaptation: ln_1 -> QKV -> attention over frames -> out_proj -> T_Adapter -> + drop_path
-    xl = _empty((M, D), BF16, dev)
-    mean1, rstd1 = _empty((M,), F32, dev), _empty((M,), F32, dev)
-    ops.layernorm_fwd(x, fz.g1, fz.b1, M, D, D, y_bf16=xl, mean=mean1, rstd=rstd1)
-    qkv_t = _empty((M, 3 * D), BF16, dev)
-    ops.gemm(xl, fz.Wqkv, ops.EPI_BF16, qkv_t, bias=fz.bqkv)
-    ot = _empty((M, D), BF16, dev)
-    probs = _empty((B * N, H, T, T), F32, dev)
-    ops.tattn_fwd(qkv_t, ot, probs, B, T, N, H)
-    ta = _empty((M, D), BF16, dev)
-    ops.gemm(ot, fz.Wo, ops.EPI_BF16, ta, bias=fz.bo)
-    del ot, xl
-    # the DropPath factor is folded into the stored activation (t_hs = dp1 * GELU(pre)), so the D_fc2 weight gradient is
-    # a plain product and the bias rides along token-scaled as `vec`
-    t_pre, t_hs = _empty((M, r), BF16, dev), _empty((M, r), BF16, dev)
-    ops.gemm(ta, tad.W1, ops.EPI_ACT, t_hs, bias=tad.b1, out2=t_pre, act=ops.ACT_GELU, at=dp1, ntok=N)
-    x1 = _empty((M, D), F32, dev)
-    ops.gemm(t_hs, tad.W2, ops.EPI_F32, x1, resid=x, vec=tad.b2.reshape(1, -1), ldv=0, bt=dp1, ntok=N)
-    # ---- spatial adaptation: ln_1 -> QKV -> attention over tokens -> out_proj -> S_Adapter (with skip)
+    t_pre, t_hs = _empty((M, r), BF16, x.device), _empty((M, r), BF16, x.device)
+    ops.gemm(ta, tad.W1, ops.EPI_ACT, t_hs, bias=tad.b1, out2=t_pre, act=ops.ACT_GELU, at=dp1, ntok=ntok)
+    x1 = _empty((M, D), F32, x.device)
+    ops.gemm(t_hs, tad.W2, ops.EPI_F32, x1, resid=x, vec=tad.b2.reshape(1, -1), ldv=0, bt=dp1, ntok=ntok)
+    return t_pre, t_hs, x1
+
+
+def _t_adapter_backward(dx1b, c, tad: _AdapterW, gT, later, ntok, r):
+    """x1 = x + t_hs W2^T + dp1[tok] b2,  t_hs = dp1[tok] GELU(ta W1^T + b1):  d(loss)/d(x1) -> d(loss)/d(ta)"""
+    M, D = dx1b.shape
+    t_hs, t_pre, ta, dp1 = c["t_hs"], c["t_pre"], c["ta"], c["dp1"]
+    later.append(lambda: ops.wgrad(dx1b, t_hs, gT["D_fc2.weight"], gT["D_fc2.bias"], at=dp1, ntok=ntok))
+    dth_pre = _empty((M, r), BF16, dx1b.device)
+    ops.gemm(dx1b, tad.W2T, ops.EPI_DACT, dth_pre, aux=t_pre, act=ops.ACT_GELU, at=dp1, ntok=ntok)
+    later.append(lambda: ops.wgrad(dth_pre, ta, gT["D_fc1.weight"], gT["D_fc1.bias"]))
+    dta = _empty((M, D), BF16, dx1b.device)
+    ops.gemm(dth_pre, tad.W1T, ops.EPI_BF16, dta)
+    return dta
+
+
+def _spatial_forward(x1, fz: _Frozen, sad: _AdapterW, BT, n, H, r):
+    """spatial adaptation over the n token rows of a frame: ln_1 -> QKV -> attention over tokens -> out_proj -> S_Adapter
+    (with skip) -> x2, and what the backward reads"""
+    dev = x1.device
+    M, D = x1.shape
     xl2 = _empty((M, D), BF16, dev)
     mean1b, rstd1b = _empty((M,), F32, dev), _empty((M,), F32, dev)
     ops.layernorm_fwd(x1, fz.g1, fz.b1, M, D, D, y_bf16=xl2, mean=mean1b, rstd=rstd1b)
-    qkv_s = _empty((M, 3 * D), BF16, dev)
-    ops.gemm(xl2, fz.Wqkv, ops.EPI_BF16, qkv_s, bias=fz.bqkv)
+    qkv2 = _empty((M, 3 * D), BF16, dev)
+    ops.gemm(xl2, fz.Wqkv, ops.EPI_BF16, qkv2, bias=fz.bqkv)
     del xl2
     ao = _empty((M, D), BF16, dev)
-    lse = _empty((BT, H, N), F32, dev)
-    ops.attn_fwd(qkv_s, ao, lse, BT, N, H)
+    lse = _empty((BT, H, n), F32, dev)
+    ops.attn_fwd(qkv2, ao, lse, BT, n, H)
     sa = _empty((M, D), BF16, dev)
     ops.gemm(ao, fz.Wo, ops.EPI_BF16, sa, bias=fz.bo)
     s_pre, s_h = _empty((M, r), BF16, dev), _empty((M, r), BF16, dev)
@@ -91,27 +98,14 @@ def aim_block_forward(x, fz: _Frozen, adp: Dict[str, _AdapterW], B, T, N, H, dp1
     x2 = _empty((M, D), F32, dev)
     ops.gemm(s_h, sad.W2, ops.EPI_F32, x2, bias=sad.b2, resid=x1)      # x1 + D_fc2(GELU(D_fc1(sa)))
     ops.acc_bf16(x2, sa)                                                # + sa: the adapter's skip connection
-    # ---- joint adaptation (shared with the vit_clip block)
-    x3, xn, mean2, rstd2, hcat_pre, a_s = _mlp_adapter_forward(x2, fz, dms2, N, save)
-    ctx = None
-    if save:
-        ctx = dict(x=x, mean1=mean1, rstd1=rstd1, qkv_t=qkv_t, probs=probs, ta=ta, t_pre=t_pre, t_hs=t_hs, x1=x1,
-                   mean1b=mean1b, rstd1b=rstd1b, qkv_s=qkv_s, ao=ao, lse=lse, sa=sa, s_pre=s_pre, s_h=s_h, x2=x2,
-                   mean2=mean2, rstd2=rstd2, xn=xn, hcat_pre=hcat_pre, a_s=a_s, dp1=dp1, dms2=dms2)
-    return x3, ctx
+    return x2, dict(x1=x1, mean1b=mean1b, rstd1b=rstd1b, qkv2=qkv2, ao=ao, lse=lse, sa=sa, s_pre=s_pre, s_h=s_h)
 
 
-def aim_block_backward(dyb, c, fz: _Frozen, adp: Dict[str, _AdapterW], grads, B, T, N, H, keep: Optional[list] = None):
-    """dyb = d(loss)/d(x3) [M, D] bf16 -> d(loss)/d(x) bf16; the 12 adapter gradients are accumulated into ``grads``
-    (their kernels run on the detached stream, joined at the end of the backward)."""
-    dev = dyb.device
-    M, D = dyb.shape
-    BT, r = B * T, fz.r
-    tad, sad = adp["T_Adapter"], adp["S_Adapter"]
-    gS, gT = grads["S_Adapter"], grads["T_Adapter"]
-    dx2b, later = _mlp_adapter_backward(dyb, c["x2"], c["mean2"], c["rstd2"], c["xn"], c["hcat_pre"], c["a_s"], c["dms2"],
-                                        fz, grads["MLP_Adapter"], N)
-    # ---- x2 = x1 + sa + (s_h W2^T + b2),  s_h = GELU(sa W1^T + b1),  sa = ao Wo^T + bo
+def _spatial_backward(dx2b, c, fz: _Frozen, sad: _AdapterW, gS, later, BT, n, H, r):
+    """x2 = x1 + sa + (s_h W2^T + b2),  s_h = GELU(sa W1^T + b1),  sa = ao Wo^T + bo:  d(loss)/d(x2) -> d(loss)/d(x1), and the
+    d(qkv), delta and dxl buffers for the temporal step to overwrite"""
+    dev = dx2b.device
+    M, D = dx2b.shape
     s_h, s_pre, sa = c["s_h"], c["s_pre"], c["sa"]
     later.append(lambda: ops.wgrad(dx2b, s_h, gS["D_fc2.weight"], gS["D_fc2.bias"]))
     dsh_pre = _empty((M, r), BF16, dev)
@@ -124,28 +118,63 @@ def aim_block_backward(dyb, c, fz: _Frozen, adp: Dict[str, _AdapterW], grads, B,
     ops.gemm(dsa, fz.WoT, ops.EPI_BF16, dao)
     del dsa
     dqkv = _empty((M, 3 * D), BF16, dev)
-    delta = _empty((BT, H, N), F32, dev)
-    ops.attn_bwd(c["qkv_s"], c["ao"], dao, c["lse"], delta, dqkv, BT, N, H)
+    delta = _empty((BT, H, n), F32, dev)
+    ops.attn_bwd(c["qkv2"], c["ao"], dao, c["lse"], delta, dqkv, BT, n, H)
     del dao
-    dxl2 = _empty((M, D), BF16, dev)
-    ops.gemm(dqkv, fz.WqkvT, ops.EPI_BF16, dxl2)
+    dxl = _empty((M, D), BF16, dev)
+    ops.gemm(dqkv, fz.WqkvT, ops.EPI_BF16, dxl)
     dx1b = _empty((M, D), BF16, dev)
-    ops.layernorm_bwd(dxl2, c["x1"], fz.g1, c["mean1b"], c["rstd1b"], M, D, lddy=D, ldx=D, lddx=D, dres=dx2b, dx_bf16=dx1b)
-    del dxl2
-    # ---- x1 = x + t_hs W2^T + dp1[tok] b2,  t_hs = dp1[tok] GELU(ta W1^T + b1),  ta = attention_T(ln_1(x)) Wo^T + bo
-    t_hs, t_pre, ta, dp1 = c["t_hs"], c["t_pre"], c["ta"], c["dp1"]
-    later.append(lambda: ops.wgrad(dx1b, t_hs, gT["D_fc2.weight"], gT["D_fc2.bias"], at=dp1, ntok=N))
-    dth_pre = _empty((M, r), BF16, dev)
-    ops.gemm(dx1b, tad.W2T, ops.EPI_DACT, dth_pre, aux=t_pre, act=ops.ACT_GELU, at=dp1, ntok=N)
-    later.append(lambda: ops.wgrad(dth_pre, ta, gT["D_fc1.weight"], gT["D_fc1.bias"]))
-    dta = _empty((M, D), BF16, dev)
-    ops.gemm(dth_pre, tad.W1T, ops.EPI_BF16, dta)
+    ops.layernorm_bwd(dxl, c["x1"], fz.g1, c["mean1b"], c["rstd1b"], M, D, lddy=D, ldx=D, lddx=D, dres=dx2b, dx_bf16=dx1b)
+    return dx1b, dqkv, delta, dxl
+
+
+def aim_block_forward(x, fz: _Frozen, adp: Dict[str, _AdapterW], B, T, N, H, dp1, dms2, save: bool):
+    """x: [B*T*N, D] f32 frame-major -> x3.  ``dp1``: the first DropPath factor per token (no adapter scale,
+    vitclip_aim.py:205); ``dms2``: the second one times ``scale`` (:210)."""
+    dev = x.device
+    M, D = x.shape
+    BT, r = B * T, fz.r
+    # ---- temporal adaptation: ln_1 -> QKV -> attention over frames -> out_proj -> T_Adapter -> + drop_path
+    xl = _empty((M, D), BF16, dev)
+    mean1, rstd1 = _empty((M,), F32, dev), _empty((M,), F32, dev)
+    ops.layernorm_fwd(x, fz.g1, fz.b1, M, D, D, y_bf16=xl, mean=mean1, rstd=rstd1)
+    qkv_t = _empty((M, 3 * D), BF16, dev)
+    ops.gemm(xl, fz.Wqkv, ops.EPI_BF16, qkv_t, bias=fz.bqkv)
+    ot = _empty((M, D), BF16, dev)
+    probs = _empty((B * N, H, T, T), F32, dev)
+    ops.tattn_fwd(qkv_t, ot, probs, B, T, N, H)
+    ta = _empty((M, D), BF16, dev)
+    ops.gemm(ot, fz.Wo, ops.EPI_BF16, ta, bias=fz.bo)
+    del ot, xl
+    t_pre, t_hs, x1 = _t_adapter_forward(ta, x, adp["T_Adapter"], dp1, N, r)
+    # ---- spatial adaptation
+    x2, c = _spatial_forward(x1, fz, adp["S_Adapter"], BT, N, H, r)
+    # ---- joint adaptation (shared with the vit_clip block)
+    x3, xn, mean2, rstd2, hcat_pre, a_s = _mlp_adapter_forward(x2, fz, dms2, N, save)
+    if not save:
+        return x3, None
+    c.update(x=x, mean1=mean1, rstd1=rstd1, qkv_t=qkv_t, probs=probs, ta=ta, t_pre=t_pre, t_hs=t_hs, x2=x2, mean2=mean2,
+             rstd2=rstd2, xn=xn, hcat_pre=hcat_pre, a_s=a_s, dp1=dp1, dms2=dms2)
+    return x3, c
+
+
+def aim_block_backward(dyb, c, fz: _Frozen, adp: Dict[str, _AdapterW], grads, B, T, N, H, keep: Optional[list] = None):
+    """dyb = d(loss)/d(x3) [M, D] bf16 -> d(loss)/d(x) bf16; the 12 adapter gradients are accumulated into ``grads``
+    (their kernels run on the detached stream, joined at the end of the backward)."""
+    dev = dyb.device
+    M, D = dyb.shape
+    BT, r = B * T, fz.r
+    dx2b, later = _mlp_adapter_backward(dyb, c["x2"], c["mean2"], c["rstd2"], c["xn"], c["hcat_pre"], c["a_s"], c["dms2"],
+                                        fz, grads["MLP_Adapter"], N)
+    dx1b, dqkv = _spatial_backward(dx2b, c, fz, adp["S_Adapter"], grads["S_Adapter"], later, BT, N, H, r)[:2]
+    # ---- ta = attention_T(ln_1(x)) Wo^T + bo
+    dta = _t_adapter_backward(dx1b, c, adp["T_Adapter"], grads["T_Adapter"], later, N, r)
     dot = _empty((M, D), BF16, dev)
     ops.gemm(dta, fz.WoT, ops.EPI_BF16, dot)
     del dta
     ops.tattn_bwd(c["qkv_t"], c["probs"], dot, dqkv, B, T, N, H)      # (re-uses the spatial branch's d(qkv) buffer)
     del dot
-    dxl = _empty((M, D), BF16, dev)
+    dxl = _empty((M, D), BF16, dev)     # not the spatial step's: held across the stretch above it would add to the step's peak
     ops.gemm(dqkv, fz.WqkvT, ops.EPI_BF16, dxl)
     del dqkv
     dxb = _empty((M, D), BF16, dev)
@@ -169,64 +198,21 @@ def aim_win_block_forward(x, fz: _Frozen, adp: Dict[str, _AdapterW], B, T, N, P,
     """x [B*T*P, D] f32 (P = N + 1 with the prompt: row N of every frame is its slot) -> x3, ctx.  ``dp1``, ``dms2`` [P]: the
     two DropPath factors per token position (``dms2`` times the adapter scale; 0 at the slot).  ``shift``: None (plain windows)
     or the (st, sh, sw) at which every axis of this block's windows is cut."""
-    dev = x.device
-    M, D = x.shape
     BT, r = B * T, fz.r
-    prompt = P != N
-    xv = lambda t: t.view(BT, P, -1)
-    tad, sad = adp["T_Adapter"], adp["S_Adapter"]
-    # ---- 1: ln_1 and the QKV projection over every row
-    xl = _empty((M, D), BF16, dev)
-    mean1, rstd1 = _empty((M,), F32, dev), _empty((M,), F32, dev)
-    ops.layernorm_fwd(x, fz.g1, fz.b1, M, D, D, y_bf16=xl, mean=mean1, rstd=rstd1)
-    qkv = _empty((M, 3 * D), BF16, dev)
-    ops.gemm(xl, fz.Wqkv, ops.EPI_BF16, qkv, bias=fz.bqkv)
-    del xl
-    # ---- 2, 3: window attention on the patch rows, class-token attention on the class rows, into one [M, D] buffer
-    at_ = _empty((M, D), BF16, dev)
-    lse_w = _empty((BT, H, P), F32, dev)
-    if shift is None:
-        ops.win_attn_fwd(qkv, at_, lse_w, B, T, N, H, window, P=P)
-    else:
-        ops.win_attn_fwd_cut(qkv, at_, lse_w, B, T, N, H, window, shift, P=P)
-    ot, probs = _empty((BT, D), BF16, dev), _empty((B, H, T, T), F32, dev)
-    ops.cls_attn_fwd(qkv, ot, probs, B, T, P, H)
-    xv(at_)[:, 0] = ot
-    if prompt:
-        xv(at_)[:, N] = 0
-    # ---- 4: out_proj, T_Adapter under the first DropPath (folded into the stored activation, as in aim_block_forward)
-    ta = _empty((M, D), BF16, dev)
-    ops.gemm(at_, fz.Wo, ops.EPI_BF16, ta, bias=fz.bo)
-    t_pre, t_hs = _empty((M, r), BF16, dev), _empty((M, r), BF16, dev)
-    ops.gemm(ta, tad.W1, ops.EPI_ACT, t_hs, bias=tad.b1, out2=t_pre, act=ops.ACT_GELU, at=dp1, ntok=P)
-    x1 = _empty((M, D), F32, dev)
-    ops.gemm(t_hs, tad.W2, ops.EPI_F32, x1, resid=x, vec=tad.b2.reshape(1, -1), ldv=0, bt=dp1, ntok=P)
-    # ---- 5: the prompt token, spatial attention over the P tokens of a frame, S_Adapter (with skip)
-    if prompt:
-        xv(x1)[:, N] = xv(ta)[:, 0]
-    xl2 = _empty((M, D), BF16, dev)
-    mean1b, rstd1b = _empty((M,), F32, dev), _empty((M,), F32, dev)
-    ops.layernorm_fwd(x1, fz.g1, fz.b1, M, D, D, y_bf16=xl2, mean=mean1b, rstd=rstd1b)
-    qkv2 = _empty((M, 3 * D), BF16, dev)
-    ops.gemm(xl2, fz.Wqkv, ops.EPI_BF16, qkv2, bias=fz.bqkv)
-    del xl2
-    ao = _empty((M, D), BF16, dev)
-    lse = _empty((BT, H, P), F32, dev)
-    ops.attn_fwd(qkv2, ao, lse, BT, P, H)
-    sa = _empty((M, D), BF16, dev)
-    ops.gemm(ao, fz.Wo, ops.EPI_BF16, sa, bias=fz.bo)
-    s_pre, s_h = _empty((M, r), BF16, dev), _empty((M, r), BF16, dev)
-    ops.gemm(sa, sad.W1, ops.EPI_ACT, s_h, bias=sad.b1, out2=s_pre, act=ops.ACT_GELU)
-    x2 = _empty((M, D), F32, dev)
-    ops.gemm(s_h, sad.W2, ops.EPI_F32, x2, bias=sad.b2, resid=x1)      # x1 + D_fc2(GELU(D_fc1(sa)))
-    ops.acc_bf16(x2, sa)                                                # + sa: the adapter's skip connection
+    # ---- 1, 2, 3 and out_proj (win_block.py)
+    ta, c = win_temporal_forward(x, fz, B, T, N, P, H, window, shift, True)
+    # ---- 4: T_Adapter under the first DropPath
+    t_pre, t_hs, x1 = _t_adapter_forward(ta, x, adp["T_Adapter"], dp1, P, r)
+    # ---- 5: the prompt token, then the stock block's spatial step over the P tokens of a frame
+    if P != N:
+        x1.view(BT, P, -1)[:, N] = ta.view(BT, P, -1)[:, 0]
+    x2, cs = _spatial_forward(x1, fz, adp["S_Adapter"], BT, P, H, r)
     # ---- 6: joint adaptation
     x3, xn, mean2, rstd2, hcat_pre, a_s = _mlp_adapter_forward(x2, fz, dms2, P, save)
     if not save:
         return x3, None
-    c = dict(x=x, mean1=mean1, rstd1=rstd1, qkv=qkv, at=at_, lse_w=lse_w, probs=probs, ta=ta, t_pre=t_pre, t_hs=t_hs, x1=x1,
-             mean1b=mean1b, rstd1b=rstd1b, qkv2=qkv2, ao=ao, lse=lse, sa=sa, s_pre=s_pre, s_h=s_h, x2=x2, mean2=mean2,
-             rstd2=rstd2, xn=xn, hcat_pre=hcat_pre, a_s=a_s, dp1=dp1, dms2=dms2)
+    c.update(cs, x=x, ta=ta, t_pre=t_pre, t_hs=t_hs, x2=x2, mean2=mean2, rstd2=rstd2, xn=xn, hcat_pre=hcat_pre, a_s=a_s,
+             dp1=dp1, dms2=dms2)
     return x3, c
 
 
@@ -234,70 +220,17 @@ def aim_win_block_backward(dyb, c, fz: _Frozen, adp: Dict[str, _AdapterW], grads
                            keep: Optional[list]):
     """dyb = d(loss)/d(x3) [M, D] bf16 with a zero slot row in every frame -> d(loss)/d(x) with the same property; the 12
     adapter gradients are accumulated into ``grads``.  ``shift``: what the block's forward was given."""
-    dev = dyb.device
-    M, D = dyb.shape
     BT, r = B * T, fz.r
-    prompt = P != N
-    xv = lambda t: t.view(BT, P, -1)
-    fork = _Fork(dev, "bwd")
-    tad, sad = adp["T_Adapter"], adp["S_Adapter"]
-    gS, gT = grads["S_Adapter"], grads["T_Adapter"]
+    fork = _Fork(dyb.device, "bwd")
     dx2b, later = _mlp_adapter_backward(dyb, c["x2"], c["mean2"], c["rstd2"], c["xn"], c["hcat_pre"], c["a_s"], c["dms2"],
                                         fz, grads["MLP_Adapter"], P)
-    # ---- 5: x2 = x' + sa + (s_h W2^T + b2),  s_h = GELU(sa W1^T + b1),  sa = ao Wo^T + bo  (the slot's rows of dx2b are zero)
-    s_h, s_pre, sa = c["s_h"], c["s_pre"], c["sa"]
-    later.append(lambda: ops.wgrad(dx2b, s_h, gS["D_fc2.weight"], gS["D_fc2.bias"]))
-    dsh_pre = _empty((M, r), BF16, dev)
-    ops.gemm(dx2b, sad.W2T, ops.EPI_DACT, dsh_pre, aux=s_pre, act=ops.ACT_GELU)
-    later.append(lambda: ops.wgrad(dsh_pre, sa, gS["D_fc1.weight"], gS["D_fc1.bias"]))
-    dsa = _empty((M, D), BF16, dev)
-    ops.gemm(dsh_pre, sad.W1T, ops.EPI_BF16, dsa)
-    ops.add_bf16(dsa, dx2b, dsa)                     # + the skip connection's share
-    dao = _empty((M, D), BF16, dev)
-    ops.gemm(dsa, fz.WoT, ops.EPI_BF16, dao)
-    del dsa
-    dqkv = _empty((M, 3 * D), BF16, dev)
-    delta = _empty((BT, H, P), F32, dev)
-    ops.attn_bwd(c["qkv2"], c["ao"], dao, c["lse"], delta, dqkv, BT, P, H)
-    del dao
-    dxl = _empty((M, D), BF16, dev)
-    ops.gemm(dqkv, fz.WqkvT, ops.EPI_BF16, dxl)
-    dx1b = _empty((M, D), BF16, dev)
-    ops.layernorm_bwd(dxl, c["x1"], fz.g1, c["mean1b"], c["rstd1b"], M, D, lddy=D, ldx=D, lddx=D, dres=dx2b, dx_bf16=dx1b)
-    dprompt = None
-    if prompt:          # the slot's row IS d(prompt) = one more gradient of ta's class rows; nothing else flows through the slot
-        dprompt = xv(dx1b)[:, N].to(F32, copy=True).contiguous()
-        xv(dx1b)[:, N] = 0
-    # ---- 4: x1 = x + t_hs W2^T + dp1[tok] b2,  t_hs = dp1[tok] GELU(ta W1^T + b1),  ta = [cls_attn | windows_attn] Wo^T + bo
-    t_hs, t_pre, ta, dp1 = c["t_hs"], c["t_pre"], c["ta"], c["dp1"]
-    later.append(lambda: ops.wgrad(dx1b, t_hs, gT["D_fc2.weight"], gT["D_fc2.bias"], at=dp1, ntok=P))
-    dth_pre = _empty((M, r), BF16, dev)
-    ops.gemm(dx1b, tad.W2T, ops.EPI_DACT, dth_pre, aux=t_pre, act=ops.ACT_GELU, at=dp1, ntok=P)
-    later.append(lambda: ops.wgrad(dth_pre, ta, gT["D_fc1.weight"], gT["D_fc1.bias"]))
-    dta = _empty((M, D), BF16, dev)
-    ops.gemm(dth_pre, tad.W1T, ops.EPI_BF16, dta)
-    if prompt:
-        ops.add_rows(dta, P * D, dprompt)             # class rows: row 0 of every frame
-    dat = _empty((M, D), BF16, dev)
-    ops.gemm(dta, fz.WoT, ops.EPI_BF16, dat)
-    del dta
-    # ---- 2, 3: the two attentions write disjoint rows of d(qkv): the window kernel the patch rows, cls_attn_bwd ADDS into
-    # the class rows (zeroed first, with the slot's)
-    xv(dqkv)[:, 0] = 0
-    if prompt:
-        xv(dqkv)[:, N] = 0
-    if shift is None:
-        ops.win_attn_bwd(c["qkv"], c["at"], dat, c["lse_w"], delta, dqkv, B, T, N, H, window, P=P)
-    else:
-        ops.win_attn_bwd_cut(c["qkv"], c["at"], dat, c["lse_w"], delta, dqkv, B, T, N, H, window, shift, P=P)
-    ops.cls_attn_bwd(c["qkv"], c["probs"], xv(dat)[:, 0].contiguous(), dqkv, B, T, P, H)
-    del dat
-    ops.gemm(dqkv, fz.WqkvT, ops.EPI_BF16, dxl)
-    del dqkv
-    dxb = _empty((M, D), BF16, dev)
-    ops.layernorm_bwd(dxl, c["x"], fz.g1, c["mean1"], c["rstd1"], M, D, lddy=D, ldx=D, lddx=D, dres=dx1b, dx_bf16=dxb)
-    if prompt:
-        xv(dxb)[:, N] = 0
+    # ---- 5 (the slot's rows of dx2b are zero)
+    dx1b, dqkv, delta, dxl = _spatial_backward(dx2b, c, fz, adp["S_Adapter"], grads["S_Adapter"], later, BT, P, H, r)
+    dprompt = win_prompt_grad(dx1b, BT, N, P)
+    # ---- 4
+    dta = _t_adapter_backward(dx1b, c, adp["T_Adapter"], grads["T_Adapter"], later, P, r)
+    # ---- out_proj, 3, 2, 1 (win_block.py), on the spatial step's d(qkv), delta and dxl buffers
+    dxb = win_temporal_backward(dta, dx1b, c, fz, dqkv, delta, dxl, B, T, N, P, H, window, shift, True, dprompt)
     _wgrads_beside(fork, later, keep)
     return dxb
 
@@ -320,12 +253,7 @@ class _AimWinFn(torch.autograd.Function):
         frozen = model._frozen_operands()
         adp = model._stage_adapters(frozen, params)
         tok, x0, mean0, rstd0, tmp = _embed_forward(model, frozen, imgs, temporal)
-        if P != N:          # once per forward: into the P-row layout (row N = the prompt's slot, zero until block 0 fills it)
-            x = _empty((BT * P, D), F32, dev)
-            x.view(BT, P, D)[:, :N] = x0.view(BT, N, D)
-            x.view(BT, P, D)[:, N] = 0
-        else:
-            x = x0
+        x = to_slot_layout(x0, BT, N, P)
         del x0
         if model.inference_precision == 'fp8' and not need_grad and not getattr(model, "_fp8_warned", False):
             model._fp8_warned = True
@@ -368,8 +296,7 @@ class _AimWinFn(torch.autograd.Function):
                                          s["window"], s["shifts"][i], keep)
             s["ctxs"][i] = None
             gbufs.layer_ready(i)
-        if P != N:          # once per backward: back to the embedding's N tokens per frame (the slot's row is zero)
-            dxb = dxb.view(BT, P, D)[:, :N].contiguous().view(BT * N, D)
+        dxb = from_slot_layout(dxb, BT, N, P)
         grads = _embed_backward(gbufs, frozen, s, dxb, keep, B, T, N, D)
         ctx.saved = None
         return grads
@@ -389,14 +316,8 @@ class AIM(ViT_CLIP):
         if num_tadapter != 1:
             raise NotImplementedError("AIM(num_tadapter=2) (T_Adapter_in, vitclip_aim.py:201-202) is not built")
         if wind_attn:
-            G = input_resolution // patch_size
-            win = clip_window(window_size, num_frames, G) if len(tuple(window_size)) == 3 else ()
-            if len(win) != 3 or any(w <= 0 for w in win) or num_frames % win[0] or G % win[1] or G % win[2]:
-                raise ValueError(f"window_size={tuple(window_size)} (clipped to {win}) does not divide the {num_frames} x {G} x {G} "
-                                 "grid (the reference zero-pads such a grid; no recipe does that and it is not built)")
-            if win[0] * win[1] * win[2] > ops.WIN_ATTN_MAX_S:
-                raise ValueError(f"{win[0] * win[1] * win[2]} tokens per window: the window attention kernels take at most "
-                                 f"{ops.WIN_ATTN_MAX_S}")
+            check_window(window_size, num_frames, input_resolution // patch_size,
+                         " (the reference zero-pads such a grid; no recipe does that and it is not built)")
         super().__init__(input_resolution, num_frames, patch_size, width, layers, heads, drop_path_rate,
                          adapter_scale=adapter_scale, pretrained=pretrained)
         self.variant = 'aim'
@@ -424,10 +345,7 @@ class AIM(ViT_CLIP):
             return super().forward(x)
         blend = self._take_blend_check_clip(x, "AIM")
         T, N = x.shape[2], (x.shape[3] // self.patch_size) ** 2 + 1
-        if N + int(self.prompt) > 288:
-            raise ValueError(f"{N + int(self.prompt)} tokens per frame: the spatial attention kernels take at most 288")
-        if T > 32:
-            raise ValueError(f"{T} frames: the class-token attention kernels take at most 32")
+        check_win_clip(T, N, self.prompt)
         x = self._arm_clip(x, blend)
         y = _AimWinFn.apply(self, torch.is_grad_enabled(), x, *self._trainable_list())     # [B, D, T]
         return y.unsqueeze(-1).unsqueeze(-1)

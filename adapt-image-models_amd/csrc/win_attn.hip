@@ -31,6 +31,8 @@
 //
 // Tails: streamed rows past S are zero-filled by the buffer bounds check (AIM_OOB) and their probabilities forced to 0; own
 // tokens past S load the window's last token and are not stored.
+#include <stdio.h>
+
 #include "aim_common.h"
 #include "aim_kernels_internal.h"
 
@@ -406,35 +408,58 @@ int win_geom(const char* who, WinGeom* g, dim3* grid, int* threads, int B, int T
     return 0;
 }
 
+// "aim_<who><part>", the name AIM_CHECK_LAUNCH gives a failed launch (the macro evaluates it only then)
+const char* launch_name(char (&buf)[48], const char* who, const char* part) {
+    snprintf(buf, sizeof buf, "aim_%s%s", who, part);
+    return buf;
+}
+
+// the host side of the three forward entries: WIN_CUT is the mode whose t axis is cut, the other two leave it whole
+template <int MODE>
+int launch_fwd(const char* who, const aim_bf16* qkv, aim_bf16* out, float* lse, int B, int T, int N, int P, int H, int wt, int wh,
+               int ww, int st, int sh, int sw, void* stream) {
+    WinGeom g;
+    dim3 grid;
+    int threads;
+    char name[48];
+    if (int rc = win_geom(who, &g, &grid, &threads, B, T, N, P, H, wt, wh, ww, st, sh, sw, MODE == WIN_CUT)) return rc;
+    AIM_CHECK_ARG(qkv && out && lse, "%s: null pointer", who);
+    hipLaunchKernelGGL(win_attn_fwd_kernel<MODE>, grid, dim3(threads), 0, (hipStream_t)stream, (const bf16_t*)qkv, (bf16_t*)out, lse,
+                       g);
+    AIM_CHECK_LAUNCH(launch_name(name, who, ""));
+    return 0;
+}
+
+// ... and of the three backward entries
+template <int MODE>
+int launch_bwd(const char* who, const aim_bf16* qkv, const aim_bf16* out, const aim_bf16* dout, const float* lse, float* delta,
+               aim_bf16* dqkv, int B, int T, int N, int P, int H, int wt, int wh, int ww, int st, int sh, int sw, void* stream) {
+    WinGeom g;
+    dim3 grid;
+    int threads;
+    char name[48];
+    if (int rc = win_geom(who, &g, &grid, &threads, B, T, N, P, H, wt, wh, ww, st, sh, sw, MODE == WIN_CUT)) return rc;
+    AIM_CHECK_ARG(qkv && out && dout && lse && delta && dqkv, "%s: null pointer", who);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(win_attn_dq_kernel<MODE>, grid, dim3(threads), 0, s, (const bf16_t*)qkv, (const bf16_t*)out,
+                       (const bf16_t*)dout, lse, delta, (bf16_t*)dqkv, g);
+    AIM_CHECK_LAUNCH(launch_name(name, who, "(dq)"));
+    hipLaunchKernelGGL(win_attn_dkv_kernel<MODE>, grid, dim3(threads), 0, s, (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta,
+                       (bf16_t*)dqkv, g);
+    AIM_CHECK_LAUNCH(launch_name(name, who, "(dkv)"));
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int aim_win_attn_fwd(const aim_bf16* qkv, aim_bf16* out, float* lse, int B, int T, int N, int P, int H, int wt,
                                 int wh, int ww, void* stream) {
-    WinGeom g;
-    dim3 grid;
-    int threads;
-    if (int rc = win_geom("win_attn_fwd", &g, &grid, &threads, B, T, N, P, H, wt, wh, ww)) return rc;
-    AIM_CHECK_ARG(qkv && out && lse, "win_attn_fwd: null pointer");
-    hipLaunchKernelGGL(win_attn_fwd_kernel<WIN_PLAIN>, grid, dim3(threads), 0, (hipStream_t)stream, (const bf16_t*)qkv, (bf16_t*)out, lse, g);
-    AIM_CHECK_LAUNCH("aim_win_attn_fwd");
-    return 0;
+    return launch_fwd<WIN_PLAIN>("win_attn_fwd", qkv, out, lse, B, T, N, P, H, wt, wh, ww, 0, 0, 0, stream);
 }
 
 extern "C" int aim_win_attn_bwd(const aim_bf16* qkv, const aim_bf16* out, const aim_bf16* dout, const float* lse, float* delta,
                                 aim_bf16* dqkv, int B, int T, int N, int P, int H, int wt, int wh, int ww, void* stream) {
-    WinGeom g;
-    dim3 grid;
-    int threads;
-    if (int rc = win_geom("win_attn_bwd", &g, &grid, &threads, B, T, N, P, H, wt, wh, ww)) return rc;
-    AIM_CHECK_ARG(qkv && out && dout && lse && delta && dqkv, "win_attn_bwd: null pointer");
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(win_attn_dq_kernel<WIN_PLAIN>, grid, dim3(threads), 0, st, (const bf16_t*)qkv, (const bf16_t*)out, (const bf16_t*)dout,
-                       lse, delta, (bf16_t*)dqkv, g);
-    AIM_CHECK_LAUNCH("aim_win_attn_bwd(dq)");
-    hipLaunchKernelGGL(win_attn_dkv_kernel<WIN_PLAIN>, grid, dim3(threads), 0, st, (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta,
-                       (bf16_t*)dqkv, g);
-    AIM_CHECK_LAUNCH("aim_win_attn_bwd(dkv)");
-    return 0;
+    return launch_bwd<WIN_PLAIN>("win_attn_bwd", qkv, out, dout, lse, delta, dqkv, B, T, N, P, H, wt, wh, ww, 0, 0, 0, stream);
 }
 
 // Shifted windows (AIM_FLASH's odd blocks, vitclip_aim_flash.py: roll by -shift, strips along the border, attention inside each
@@ -449,33 +474,13 @@ extern "C" int aim_win_attn_bwd(const aim_bf16* qkv, const aim_bf16* out, const 
 // those of the unshifted kernels, hence their bits.
 extern "C" int aim_win_attn_fwd_shift(const aim_bf16* qkv, aim_bf16* out, float* lse, int B, int T, int N, int P, int H, int wt,
                                       int wh, int ww, int st, int sh, int sw, void* stream) {
-    WinGeom g;
-    dim3 grid;
-    int threads;
-    if (int rc = win_geom("win_attn_fwd_shift", &g, &grid, &threads, B, T, N, P, H, wt, wh, ww, st, sh, sw)) return rc;
-    AIM_CHECK_ARG(qkv && out && lse, "win_attn_fwd_shift: null pointer");
-    hipLaunchKernelGGL(win_attn_fwd_kernel<WIN_WRAP>, grid, dim3(threads), 0, (hipStream_t)stream, (const bf16_t*)qkv, (bf16_t*)out, lse,
-                       g);
-    AIM_CHECK_LAUNCH("aim_win_attn_fwd_shift");
-    return 0;
+    return launch_fwd<WIN_WRAP>("win_attn_fwd_shift", qkv, out, lse, B, T, N, P, H, wt, wh, ww, st, sh, sw, stream);
 }
 
 extern "C" int aim_win_attn_bwd_shift(const aim_bf16* qkv, const aim_bf16* out, const aim_bf16* dout, const float* lse,
                                       float* delta, aim_bf16* dqkv, int B, int T, int N, int P, int H, int wt, int wh, int ww,
                                       int st, int sh, int sw, void* stream) {
-    WinGeom g;
-    dim3 grid;
-    int threads;
-    if (int rc = win_geom("win_attn_bwd_shift", &g, &grid, &threads, B, T, N, P, H, wt, wh, ww, st, sh, sw)) return rc;
-    AIM_CHECK_ARG(qkv && out && dout && lse && delta && dqkv, "win_attn_bwd_shift: null pointer");
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(win_attn_dq_kernel<WIN_WRAP>, grid, dim3(threads), 0, s, (const bf16_t*)qkv, (const bf16_t*)out,
-                       (const bf16_t*)dout, lse, delta, (bf16_t*)dqkv, g);
-    AIM_CHECK_LAUNCH("aim_win_attn_bwd_shift(dq)");
-    hipLaunchKernelGGL(win_attn_dkv_kernel<WIN_WRAP>, grid, dim3(threads), 0, s, (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta,
-                       (bf16_t*)dqkv, g);
-    AIM_CHECK_LAUNCH("aim_win_attn_bwd_shift(dkv)");
-    return 0;
+    return launch_bwd<WIN_WRAP>("win_attn_bwd_shift", qkv, out, dout, lse, delta, dqkv, B, T, N, P, H, wt, wh, ww, st, sh, sw, stream);
 }
 
 // Cut windows (AIM's odd blocks, vitclip_aim.py: roll by -shift, attention inside whole windows of the rolled grid under an
@@ -488,31 +493,11 @@ extern "C" int aim_win_attn_bwd_shift(const aim_bf16* qkv, const aim_bf16* out, 
 // With st = 0 the items, the token order and the tile order are those of *_shift at the same (sh, sw), hence their bits.
 extern "C" int aim_win_attn_fwd_cut(const aim_bf16* qkv, aim_bf16* out, float* lse, int B, int T, int N, int P, int H, int wt,
                                     int wh, int ww, int st, int sh, int sw, void* stream) {
-    WinGeom g;
-    dim3 grid;
-    int threads;
-    if (int rc = win_geom("win_attn_fwd_cut", &g, &grid, &threads, B, T, N, P, H, wt, wh, ww, st, sh, sw, true)) return rc;
-    AIM_CHECK_ARG(qkv && out && lse, "win_attn_fwd_cut: null pointer");
-    hipLaunchKernelGGL(win_attn_fwd_kernel<WIN_CUT>, grid, dim3(threads), 0, (hipStream_t)stream, (const bf16_t*)qkv, (bf16_t*)out, lse,
-                       g);
-    AIM_CHECK_LAUNCH("aim_win_attn_fwd_cut");
-    return 0;
+    return launch_fwd<WIN_CUT>("win_attn_fwd_cut", qkv, out, lse, B, T, N, P, H, wt, wh, ww, st, sh, sw, stream);
 }
 
 extern "C" int aim_win_attn_bwd_cut(const aim_bf16* qkv, const aim_bf16* out, const aim_bf16* dout, const float* lse, float* delta,
                                     aim_bf16* dqkv, int B, int T, int N, int P, int H, int wt, int wh, int ww, int st, int sh,
                                     int sw, void* stream) {
-    WinGeom g;
-    dim3 grid;
-    int threads;
-    if (int rc = win_geom("win_attn_bwd_cut", &g, &grid, &threads, B, T, N, P, H, wt, wh, ww, st, sh, sw, true)) return rc;
-    AIM_CHECK_ARG(qkv && out && dout && lse && delta && dqkv, "win_attn_bwd_cut: null pointer");
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(win_attn_dq_kernel<WIN_CUT>, grid, dim3(threads), 0, s, (const bf16_t*)qkv, (const bf16_t*)out,
-                       (const bf16_t*)dout, lse, delta, (bf16_t*)dqkv, g);
-    AIM_CHECK_LAUNCH("aim_win_attn_bwd_cut(dq)");
-    hipLaunchKernelGGL(win_attn_dkv_kernel<WIN_CUT>, grid, dim3(threads), 0, s, (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta,
-                       (bf16_t*)dqkv, g);
-    AIM_CHECK_LAUNCH("aim_win_attn_bwd_cut(dkv)");
-    return 0;
+    return launch_bwd<WIN_CUT>("win_attn_bwd_cut", qkv, out, dout, lse, delta, dqkv, B, T, N, P, H, wt, wh, ww, st, sh, sw, stream);
 }

@@ -329,71 +329,60 @@ def attn_bwd_shift(qkv, out, dout, lse, delta, dqkv, B, T, N, H, shifts):
 WIN_ATTN_MAX_S = 4096   # AIM_WIN_ATTN_MAX_S of include/aim_kernels.h (ABI 11)
 
 
+def _ints3(v):
+    a, b, c = (int(x) for x in v)
+    return a, b, c
+
+
+def _win_attn_fwd(entry, qkv, out, lse, B, T, N, H, window, shift, P):
+    """the three forward entries: ``entry`` names the library's function, ``shift`` is None for the one that takes none"""
+    _chk(qkv, BF16, "qkv"); _chk(out, BF16, "out"); _chk(lse, F32, "lse")
+    geom = _ints3(window) + (() if shift is None else _ints3(shift))
+    check(getattr(load_library(), entry)(qkv.data_ptr(), out.data_ptr(), lse.data_ptr(), B, T, N, N if P is None else P, H,
+                                         *geom, _stream()), entry)
+
+
+def _win_attn_bwd(entry, qkv, out, dout, lse, delta, dqkv, B, T, N, H, window, shift, P):
+    """the three backward entries, as ``_win_attn_fwd``"""
+    _chk(qkv, BF16, "qkv"); _chk(out, BF16, "out"); _chk(dout, BF16, "dout"); _chk(dqkv, BF16, "dqkv")
+    _chk(lse, F32, "lse"); _chk(delta, F32, "delta")
+    geom = _ints3(window) + (() if shift is None else _ints3(shift))
+    check(getattr(load_library(), entry)(qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(), delta.data_ptr(),
+                                         dqkv.data_ptr(), B, T, N, N if P is None else P, H, *geom, _stream()), entry)
+
+
 def win_attn_fwd(qkv, out, lse, B, T, N, H, window, P=None):
     """Attention inside the (wt, wh, ww) windows of the patch grid of B clips of T frames (class rows untouched); the
     partition is addressing inside the kernel.  P (default N): token rows per frame of the buffers, the rows behind a
     frame's N tokens are untouched too.  out [B*T*P, D], lse [B*T, H, P]."""
-    _chk(qkv, BF16, "qkv"); _chk(out, BF16, "out"); _chk(lse, F32, "lse")
-    wt, wh, ww = (int(w) for w in window)
-    check(load_library().aim_win_attn_fwd(qkv.data_ptr(), out.data_ptr(), lse.data_ptr(), B, T, N, N if P is None else P, H, wt, wh, ww,
-                                          _stream()),
-          "aim_win_attn_fwd")
+    _win_attn_fwd("aim_win_attn_fwd", qkv, out, lse, B, T, N, H, window, None, P)
 
 
 def win_attn_bwd(qkv, out, dout, lse, delta, dqkv, B, T, N, H, window, P=None):
     """backward of win_attn_fwd: writes the patch rows of dqkv [B*T*P, 3D] and of delta [B*T, H, P]."""
-    _chk(qkv, BF16, "qkv"); _chk(out, BF16, "out"); _chk(dout, BF16, "dout"); _chk(dqkv, BF16, "dqkv")
-    _chk(lse, F32, "lse"); _chk(delta, F32, "delta")
-    wt, wh, ww = (int(w) for w in window)
-    check(load_library().aim_win_attn_bwd(qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(), delta.data_ptr(),
-                                          dqkv.data_ptr(), B, T, N, N if P is None else P, H, wt, wh, ww, _stream()),
-          "aim_win_attn_bwd")
+    _win_attn_bwd("aim_win_attn_bwd", qkv, out, dout, lse, delta, dqkv, B, T, N, H, window, None, P)
 
 
 def win_attn_fwd_shift(qkv, out, lse, B, T, N, H, window, shift, P=None):
     """win_attn_fwd on windows shifted by (st, sh, sw): the h and w axes are cut at 0, s, s + w, ..., the t windows start at st
     and wrap round the clip's end (include/aim_kernels.h).  A zero shift gives win_attn_fwd's bits."""
-    _chk(qkv, BF16, "qkv"); _chk(out, BF16, "out"); _chk(lse, F32, "lse")
-    wt, wh, ww = (int(w) for w in window)
-    st, sh, sw = (int(s) for s in shift)
-    check(load_library().aim_win_attn_fwd_shift(qkv.data_ptr(), out.data_ptr(), lse.data_ptr(), B, T, N, N if P is None else P, H,
-                                                wt, wh, ww, st, sh, sw, _stream()),
-          "aim_win_attn_fwd_shift")
+    _win_attn_fwd("aim_win_attn_fwd_shift", qkv, out, lse, B, T, N, H, window, shift, P)
 
 
 def win_attn_bwd_shift(qkv, out, dout, lse, delta, dqkv, B, T, N, H, window, shift, P=None):
     """backward of win_attn_fwd_shift: writes the patch rows of dqkv [B*T*P, 3D] and of delta [B*T, H, P]."""
-    _chk(qkv, BF16, "qkv"); _chk(out, BF16, "out"); _chk(dout, BF16, "dout"); _chk(dqkv, BF16, "dqkv")
-    _chk(lse, F32, "lse"); _chk(delta, F32, "delta")
-    wt, wh, ww = (int(w) for w in window)
-    st, sh, sw = (int(s) for s in shift)
-    check(load_library().aim_win_attn_bwd_shift(qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(), delta.data_ptr(),
-                                                dqkv.data_ptr(), B, T, N, N if P is None else P, H, wt, wh, ww, st, sh, sw,
-                                                _stream()),
-          "aim_win_attn_bwd_shift")
+    _win_attn_bwd("aim_win_attn_bwd_shift", qkv, out, dout, lse, delta, dqkv, B, T, N, H, window, shift, P)
 
 
 def win_attn_fwd_cut(qkv, out, lse, B, T, N, H, window, shift, P=None):
     """win_attn_fwd_shift with the t axis cut like h and w, at 0, st, st + wt, ..., T, instead of wrapping round the clip's end
     (AIM's masked shifted windows; include/aim_kernels.h).  st = 0 gives win_attn_fwd_shift's bits."""
-    _chk(qkv, BF16, "qkv"); _chk(out, BF16, "out"); _chk(lse, F32, "lse")
-    wt, wh, ww = (int(w) for w in window)
-    st, sh, sw = (int(s) for s in shift)
-    check(load_library().aim_win_attn_fwd_cut(qkv.data_ptr(), out.data_ptr(), lse.data_ptr(), B, T, N, N if P is None else P, H,
-                                              wt, wh, ww, st, sh, sw, _stream()),
-          "aim_win_attn_fwd_cut")
+    _win_attn_fwd("aim_win_attn_fwd_cut", qkv, out, lse, B, T, N, H, window, shift, P)
 
 
 def win_attn_bwd_cut(qkv, out, dout, lse, delta, dqkv, B, T, N, H, window, shift, P=None):
     """backward of win_attn_fwd_cut: writes the patch rows of dqkv [B*T*P, 3D] and of delta [B*T, H, P]."""
-    _chk(qkv, BF16, "qkv"); _chk(out, BF16, "out"); _chk(dout, BF16, "dout"); _chk(dqkv, BF16, "dqkv")
-    _chk(lse, F32, "lse"); _chk(delta, F32, "delta")
-    wt, wh, ww = (int(w) for w in window)
-    st, sh, sw = (int(s) for s in shift)
-    check(load_library().aim_win_attn_bwd_cut(qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(), delta.data_ptr(),
-                                              dqkv.data_ptr(), B, T, N, N if P is None else P, H, wt, wh, ww, st, sh, sw,
-                                              _stream()),
-          "aim_win_attn_bwd_cut")
+    _win_attn_bwd("aim_win_attn_bwd_cut", qkv, out, dout, lse, delta, dqkv, B, T, N, H, window, shift, P)
 
 
 def attn_fwd_cls(qkv, out_cls, lse_cls, BT, N, H):
