@@ -671,32 +671,49 @@ def _mlp_adapter_forward(x1, fz: _Frozen, dms2, N, save: bool, small_tile: bool 
 
 
 def _mlp_adapter_backward(dyb, x_in, mean2, rstd2, xn, hcat_pre, a_s, dms2, fz: _Frozen, gm, N, fsum=None,
-                          small_tile: bool = False, af=None):
+                          small_tile: bool = False, af=None, rides: Optional[list] = None):
     """Backward of ``_mlp_adapter_forward``: returns (d(x_in) as bf16, the weight-gradient closures).  x2 = x_in +
     [h | a_s] [W_proj | W2]^T + b_proj + dms2[tok] * b2.  ``fsum = (w [N], partial [frames, LN_FSUM_GROUPS, D])``: the ln_2
-    backward also leaves the per-frame sums of w[n] * d(x_in) (in token groups) in ``partial``."""
+    backward also leaves the per-frame sums of w[n] * d(x_in) (in token groups) in ``partial``.
+
+    ``rides`` (a list, or None: never): the two big weight gradients may go as rider workgroups in the CUs this block's
+    dgrad GEMMs leave idle (``ops.WgradRide``; the library's policy decides per launch, from shapes alone).  D_fc2 is offered
+    to the DACT launch, D_fc1 to the K = 4D + r dgrad; one that its launch took is appended to ``rides`` -- the caller may
+    offer its remaining rows to later launches and must run its ``finish`` behind the last of them -- one that it did not
+    take goes the stand-alone way."""
     dev = dyb.device
     M, D = dyb.shape
     r, H4 = fz.r, 4 * D
     big_later: list = []
+    riding = rides is not None and af is None and not small_tile
+
+    def stand_alone(call):              # off the critical stream (run by the caller), or right here
+        big_later.append(call) if _DETACH_BIG else call()
+
     # D_fc2: weight gradient + the DropPath-scaled bias gradient in one pass over dyb
+    wgrad2 = lambda: ops.wgrad(dyb, a_s, gm["D_fc2.weight"], gm["D_fc2.bias"], at=dms2, ntok=N)
     if af is not None:                  # a frame factor as well: the bias gradient is a column sum of its own
         big_later.append(lambda: (ops.wgrad(dyb, a_s, gm["D_fc2.weight"]),
                                   ops.colsum(dyb, gm["D_fc2.bias"], af=af, at=dms2, ntok=N)))
-    elif _DETACH_BIG:
-        big_later.append(lambda: ops.wgrad(dyb, a_s, gm["D_fc2.weight"], gm["D_fc2.bias"], at=dms2, ntok=N))
-    else:
-        ops.wgrad(dyb, a_s, gm["D_fc2.weight"], gm["D_fc2.bias"], at=dms2, ntok=N)
+    elif not riding:
+        stand_alone(wgrad2)
+    ride2 = ops.WgradRide(dyb, a_s, gm["D_fc2.weight"], gm["D_fc2.bias"], at=dms2, ntok=N) if riding else None
     dcat = _empty((M, H4 + r), BF16, dev)           # [dh_pre | da_pre]
     ops.gemm(dyb, fz.WcatT2, ops.EPI_DACT, dcat, aux=hcat_pre, act=ops.ACT_QGELU, n_split=H4, act2=ops.ACT_GELU,
              af=af, at=dms2, ntok=N, aux_grad=_AUX_GRAD, aux_frag=_AUX_FRAG and dyb.shape[0] >= 1024 and not small_tile,
-             reserve_cus=_DP_RESERVE, small_tile=small_tile)
-    if _DETACH_BIG:
-        big_later.append(lambda: ops.wgrad(dcat[:, H4:], xn, gm["D_fc1.weight"], gm["D_fc1.bias"]))
-    else:
-        ops.wgrad(dcat[:, H4:], xn, gm["D_fc1.weight"], gm["D_fc1.bias"])
+             reserve_cus=_DP_RESERVE, small_tile=small_tile, ride=[ride2] if riding else None)
+    if riding and ride2.used:
+        rides.append(ride2)
+    elif riding:                        # the DACT launch did not take it: the stand-alone launch, as without riders
+        stand_alone(wgrad2)
+    ride1 = ops.WgradRide(dcat[:, H4:], xn, gm["D_fc1.weight"], gm["D_fc1.bias"]) if riding else None
     dxn = _empty((M, D), BF16, dev)
-    ops.gemm(dcat, fz.WcatT1, ops.EPI_BF16, dxn, reserve_cus=_DP_RESERVE, small_tile=small_tile)     # K = 4D + r: frozen c_fc dgrad + adapter D_fc1 dgrad
+    ops.gemm(dcat, fz.WcatT1, ops.EPI_BF16, dxn, reserve_cus=_DP_RESERVE, small_tile=small_tile,      # K = 4D + r: frozen c_fc dgrad + adapter D_fc1 dgrad
+             ride=rides + [ride1] if riding else None)
+    if riding and ride1.used:
+        rides.append(ride1)
+    else:
+        stand_alone(lambda: ops.wgrad(dcat[:, H4:], xn, gm["D_fc1.weight"], gm["D_fc1.bias"]))
     dxb = _empty((M, D), BF16, dev)                  # (dcat stays alive in the D_fc1 weight-gradient closure)
     if fsum is not None:
         ops.layernorm_bwd_fsum(dxn, x_in, fz.g2, mean2, rstd2, dyb, dxb, fsum[0], fsum[1], M // N, N, D)
@@ -737,12 +754,16 @@ def _block_backward(dyb, c, fz: _Frozen, adp: Dict[str, _AdapterW], grads, B, T,
     # (top form: the class row is the frame's only non-zero row of d(x1), so the sum is dms1[0] * that row)
     fsum_in_ln = _FSUM_IN_LN and not top
     fpart = _empty((BT, ops.LN_FSUM_GROUPS, D), F32, dev) if fsum_in_ln else None
+    # the big weight gradients whose rows ride in this block's dgrad launches (ops.WgradRide): what the MLP's two launches
+    # left of them is offered to the out_proj and QKV dgrads below; their sums are finished behind the last of those
+    rides: list = []
     if top:
         dx1b, big_later = _mlp_adapter_backward(dyb, c["x1"], c["mean2"], c["rstd2"], c["xn"], c["hcat_pre"], c["a_s"],
                                                 c["dms2"][:1], fz, grads["MLP_Adapter"], 1, small_tile=True)
     else:
         dx1b, big_later = _mlp_adapter_backward(dyb, c["x1"], c["mean2"], c["rstd2"], c["xn"], c["hcat_pre"], c["a_s"], c["dms2"],
-                                                fz, grads["MLP_Adapter"], N, fsum=(c["dms1"], fpart) if fsum_in_ln else None)
+                                                fz, grads["MLP_Adapter"], N, fsum=(c["dms1"], fpart) if fsum_in_ln else None,
+                                                rides=rides)
     # ---- x1 = x + oml[f] * (ao Wo^T + bo) + dms1[tok] * s_vec[f]
     # class-token chain (S_Adapter, cross term, T_Adapter; a dozen kernels on B*T rows) on the side stream ...
     later: list = big_later       # the adapters' weight gradients: nobody downstream waits for them
@@ -778,6 +799,7 @@ def _block_backward(dyb, c, fz: _Frozen, adp: Dict[str, _AdapterW], grads, B, T,
             ops.cls_attn_bwd(c["qkv"], c["probs"], dot, dqkv_cls, B, T, N, H, compact=True)
             dxl_cls = ar.take((BT, D), F32)
             ops.gemm(dqkv_cls, fz.WqkvT, ops.EPI_F32, dxl_cls)
+    detached = keep is not None
     if keep is None:       # stand-alone use: the weight gradients are complete when this function returns
         keep = []
         fork.run_detached(later, keep)
@@ -792,7 +814,7 @@ def _block_backward(dyb, c, fz: _Frozen, adp: Dict[str, _AdapterW], grads, B, T,
         ops.attn_bwd_cls(c["qkv"], c["ao"], dao, c["lse"], dqkv, BT, N, H)      # every row of dqkv: zeros in the other dQ rows
     else:
         dao = _empty((M, D), BF16, dev)
-        ops.gemm(dx1b, fz.WoT, ops.EPI_BF16, dao, af=c["oml"], ntok=N, reserve_cus=_DP_RESERVE)
+        ops.gemm(dx1b, fz.WoT, ops.EPI_BF16, dao, af=c["oml"], ntok=N, reserve_cus=_DP_RESERVE, ride=rides)
         delta = _empty((BT, H, N), F32, dev)
         ops.attn_bwd(c["qkv"], c["ao"], dao, c["lse"], delta, dqkv, BT, N, H)
     del dao
@@ -800,8 +822,10 @@ def _block_backward(dyb, c, fz: _Frozen, adp: Dict[str, _AdapterW], grads, B, T,
         fork.join()
         ops.cls_attn_bwd(c["qkv"], c["probs"], dot, dqkv, B, T, N, H)
     dxl = _empty((M, D), BF16, dev)
-    ops.gemm(dqkv, fz.WqkvT, ops.EPI_BF16, dxl, reserve_cus=_DP_RESERVE)
+    ops.gemm(dqkv, fz.WqkvT, ops.EPI_BF16, dxl, reserve_cus=_DP_RESERVE, ride=rides)
     del dqkv
+    # the riders' slabs are complete behind this launch: the rows nobody took and the sums go beside the main stream
+    _wgrads_beside(fork, [rd.finish for rd in rides], keep if detached else None)
     if _LATE_JOIN:
         fork.join()
         ops.add_rows(dxl, N * D, dxl_cls)       # class rows: rows n == 0 of every frame

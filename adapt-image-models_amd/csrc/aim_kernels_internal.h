@@ -11,8 +11,16 @@ enum { ACT_QGELU = AIM_ACT_QGELU, ACT_GELU = AIM_ACT_GELU };
 // CUs of the current device (per-call query, no cache; CU-masked caller streams are not supported: capi.hip).  Persistent
 // kernels size their grids by it.
 int aim_device_cus();
-int aim_gemm_launch(const GemmArgs& g, int epi, int batch, hipStream_t st);
+// ride != nullptr: the launch also carries the rider workgroups of an adapter weight gradient (gemm256.hip); refused unless
+// aim_gemm_hosts_riders(g, epi).  *chunks_written: the slabs the riders fill.
+int aim_gemm_launch(const GemmArgs& g, int epi, int batch, hipStream_t st, const aim_wgrad_ride_args* ride = nullptr,
+                    int* chunks_written = nullptr);
 int aim_gemm256_launch(const GemmArgs& g, int epi, int nbatch, hipStream_t st);
+bool aim_gemm_hosts_riders(const GemmArgs& g, int epi);
+int aim_gemm256_ride_launch(const GemmArgs& g, int epi, const aim_wgrad_ride_args& r, int* chunks_written, hipStream_t st);
+int aim_gemm256_ride_plan(const GemmArgs& g, int epi, int Nw, int Kw, int ntok, int M_total, int rows_left, int* chunks, int* rows);
+// a row range as at most max_chunks chunks of whole 32-row steps: the chunk length and the number of non-empty chunks
+int aim_wgrad_range_chunks(int rows, int max_chunks, int* chunk_out);
 int aim_gemm256_fp8_launch(const GemmArgs& g, int epi, hipStream_t st);
 int aim_gemm_small_launch(const GemmArgs& g, int epi, int batch, hipStream_t st);
 int aim_gemm_small_fp8_launch(const GemmArgs& g, int epi, hipStream_t st);

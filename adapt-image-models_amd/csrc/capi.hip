@@ -37,6 +37,20 @@ extern "C" int aim_gemm_bf16(const aim_gemm_args* args, int epilogue, int batch,
     return aim_gemm_launch(*args, epilogue, batch, (hipStream_t)stream);
 }
 
+extern "C" int aim_gemm_bf16_ride(const aim_gemm_args* args, int epilogue, const aim_wgrad_ride_args* ride, int* chunks_written,
+                                  void* stream) {
+    AIM_CHECK_ARG(args != nullptr && ride != nullptr, "gemm_ride: null args");
+    return aim_gemm_launch(*args, epilogue, 1, (hipStream_t)stream, ride, chunks_written);
+}
+
+extern "C" int aim_wgrad_ride_plan(const aim_gemm_args* host, int epilogue, int Nw, int Kw, int ntok, int M_total, int rows_left,
+                                   int* chunks, int* rows) {
+    AIM_CHECK_ARG(host && chunks && rows, "wgrad_ride_plan: null pointer");
+    *chunks = *rows = 0;
+    if (!aim_gemm_hosts_riders(*host, epilogue) || Nw <= 0 || Kw <= 0 || (Nw % 8) || (Kw % 8)) return 0;
+    return aim_gemm256_ride_plan(*host, epilogue, Nw, Kw, ntok, M_total, rows_left, chunks, rows);
+}
+
 extern "C" int aim_gemm_fp8(const aim_gemm_args* args, int epilogue, void* stream) {
     AIM_CHECK_ARG(args != nullptr, "gemm_fp8: null args");
     const GemmArgs& g = *args;

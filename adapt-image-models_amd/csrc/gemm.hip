@@ -198,7 +198,28 @@ int aim_gemm_peel_rows(const GemmArgs& g, int* M0) {
     return 0;
 }
 
-int aim_gemm_launch(const GemmArgs& g, int epi, int batch, hipStream_t st) {
+// the problems that run on the 256x256 pipelined kernel (gemm256.hip); AIM_GEMM_TILE=128 forces this file's.
+// Its epilogue moves 16 bytes per lane: bf16 outputs need N and the leading dimensions in multiples of 8
+// (and K in whole 64-element K-tiles: the 256x256 kernel's staging does not mask a row's K tail).
+static bool gemm_wide(const GemmArgs& g, int epi, int batch) {
+    static const int pick = [] { const char* e = getenv("AIM_GEMM_TILE"); return e ? atoi(e) : 0; }();
+    const bool wide_ok = (g.N % 8) == 0 && (g.n_split % 8) == 0 && (g.K % 64) == 0 &&
+                         (epi == EPI_F32 ? ((g.ldr % 4) == 0 && (g.ldv % 4) == 0 && (!g.vec || g.ntok >= 128))
+                                         : ((g.ldo % 8) == 0 && (epi != EPI_ACT || (g.ldo2 % 8) == 0) &&
+                                            (epi != EPI_DACT || (g.ldaux % 8) == 0)));
+    return pick != 128 && batch == 1 && epi != EPI_EXPSUM && g.M >= 1024 && g.N >= 64 && wide_ok;
+}
+
+// a launch that can host rider workgroups: one launch of the persistent kernel (not peeled), BF16 or DACT epilogue
+bool aim_gemm_hosts_riders(const GemmArgs& g, int epi) {
+    int M0 = 0;
+    return (epi == EPI_BF16 || epi == EPI_DACT) && !g.small_tile && g.row0 == 0 && g.M > 0 && g.N > 0 && g.K > 0 &&
+           gemm_wide(g, epi, 1) && !(epi == EPI_BF16 && aim_gemm_peel_rows(g, &M0) > 0);
+}
+
+int aim_gemm_launch(const GemmArgs& g, int epi, int batch, hipStream_t st, const aim_wgrad_ride_args* ride, int* chunks_written) {
+    AIM_CHECK_ARG(!ride || (batch == 1 && aim_gemm_hosts_riders(g, epi)),
+                  "gemm_ride: this launch cannot host riders (one un-peeled launch of the 256 x 256 kernel, BF16 or DACT)");
     AIM_CHECK_ARG(g.M > 0 && g.N > 0 && g.K > 0, "gemm: empty problem M=%d N=%d K=%d", g.M, g.N, g.K);
     AIM_CHECK_ARG((g.K % 8) == 0 && (g.lda % 8) == 0 && (g.ldw % 8) == 0, "gemm: K/lda/ldw must be multiples of 8 (K=%d lda=%d ldw=%d)", g.K, g.lda, g.ldw);
     AIM_CHECK_ARG(epi == EPI_EXPSUM || ((g.N % 4) == 0 && (g.ldo % 4) == 0), "gemm: N and ldo must be multiples of 4 (N=%d ldo=%d)", g.N, g.ldo);
@@ -208,15 +229,7 @@ int aim_gemm_launch(const GemmArgs& g, int epi, int batch, hipStream_t st) {
     // the epilogues pick a column's activation and row factor once per group of 4 columns (gemm_epilogue.h: col_act / col_rs)
     AIM_CHECK_ARG(g.n_split >= 0 && (g.n_split % 4) == 0 && g.n_split <= g.N,
                   "gemm: n_split must be a multiple of 4 in [0, N] (n_split=%d N=%d)", g.n_split, g.N);
-    // large-M problems run on the 256x256 pipelined kernel (gemm256.hip); AIM_GEMM_TILE=128 forces this file's.
-    // Its epilogue moves 16 bytes per lane: bf16 outputs need N and the leading dimensions in multiples of 8.
-    static const int pick = [] { const char* e = getenv("AIM_GEMM_TILE"); return e ? atoi(e) : 0; }();
-    // (and K in whole 64-element K-tiles: the 256x256 kernel's staging does not mask a row's K tail)
-    const bool wide_ok = (g.N % 8) == 0 && (g.n_split % 8) == 0 && (g.K % 64) == 0 &&
-                         (epi == EPI_F32 ? ((g.ldr % 4) == 0 && (g.ldv % 4) == 0 && (!g.vec || g.ntok >= 128))
-                                         : ((g.ldo % 8) == 0 && (epi != EPI_ACT || (g.ldo2 % 8) == 0) &&
-                                            (epi != EPI_DACT || (g.ldaux % 8) == 0)));
-    if (pick != 128 && batch == 1 && epi != EPI_EXPSUM && g.M >= 1024 && g.N >= 64 && wide_ok) {
+    if (gemm_wide(g, epi, batch)) {
         AIM_CHECK_ARG(!g.aux_frag || epi == EPI_ACT || epi == EPI_DACT, "gemm: aux_frag is an ACT / DACT option");
         AIM_CHECK_ARG(g.row0 == 0, "gemm: row0 != 0 is for launches of fewer than 1024 rows");
         // A THIN last tile round (ViT-L/14: 2 056 tiles = 8.03 rounds of 256 CUs; every N = 1 024 GEMM of the block) costs the
@@ -238,6 +251,7 @@ int aim_gemm_launch(const GemmArgs& g, int epi, int batch, hipStream_t st) {
             if (int rc = aim_gemm256_launch(head, epi, 1, st)) return rc;
             return aim_gemm_small_launch(tail, epi, 1, st);
         }
+        if (ride) return aim_gemm256_ride_launch(g, epi, *ride, chunks_written, st);
         return aim_gemm256_launch(g, epi, 1, st);
     }
     if (epi == EPI_EXPSUM && aim_expsum_use256(g.M, g.N) && (g.K % 64) == 0) {

@@ -26,6 +26,7 @@
 #include "aim_common.h"
 #include "aim_kernels_internal.h"
 #include "gemm_epilogue.h"
+#include "wgrad_tile.h"
 #include <stdlib.h>
 
 namespace {
@@ -34,6 +35,11 @@ constexpr int HT = 128 * 64 * 2;        // half-tile bytes
 constexpr int BUF = 4 * HT;             // one K-tile buffer: A_lo, A_hi, B_lo, B_hi
 constexpr int OFF_A = 0, OFF_B = 2 * HT;
 constexpr int LDS_BYTES = 2 * BUF + 8 * EPI_SCRATCH;   // K-loop images + 8 wave-private row-factor tables
+// rider 32-row steps per host K-step (aim_gemm256_ride_plan; DESIGN.md section 4: the measured ratio is 1.26, a fifth is held back)
+constexpr double AIM_WGRAD_RIDE_C_DEFAULT = 1.0;
+// a rider's LDS: the weight-gradient ring (128 KiB) and its `at` table behind it
+constexpr int RIDE_AT_BYTES = 16 * 1024;
+static_assert(LDS_BYTES >= wgrad_tile::RING_BYTES + RIDE_AT_BYTES, "no room for a rider's row-factor table");
 
 // Per-tile staging state: buffer descriptors of the tile's A rows / W rows and the per-lane row offsets.
 struct TileSrc {
@@ -79,13 +85,35 @@ __device__ __forceinline__ TileSrc make_tile(const GemmArgs& g, int tile, int nt
 // staged and read exactly like the bf16 image, and multiplied by ONE v_mfma_scale_f32_16x16x128_f8f6f4 per 16x16 tile
 // (unit block scales): the lane's two 16-byte chunks (ks = 0, 1) are its 32 k-values of that instruction -- any
 // assignment of k to lanes works as long as both operands use the same one (tools/probe_mfma_fp8.hip).
-template <int EPI, bool F8>
+//
+// RIDE: the launch has ride.gemm_wgs + (rider) workgroups.  The riders -- the highest block indices -- run one (tile, M-chunk)
+// of an adapter weight gradient each (wgrad_tile.h) in the CUs the balanced grid leaves idle, and return; they share nothing
+// with the GEMM workgroups (no flags, no atomics: a rider's slab is complete when the launch is).  The GEMM workgroups rank
+// themselves, stride their tiles and index their probe slots by ride.gemm_wgs instead of gridDim.x.  Only the variants that
+// host riders are instantiated with RIDE; the others carry an empty argument and compile to what they were.
+template <bool RIDE>
+struct RideArg {};
+template <>
+struct RideArg<true> {
+    wgrad_tile::Job job;
+    int gemm_wgs;
+};
+
+template <int EPI, bool F8, bool RIDE = false>
 __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs g, int ntiles, int nbatch, int phase_skew,
-                                                      unsigned long long* probe, int probe_cap) {
+                                                      unsigned long long* probe, int probe_cap, RideArg<RIDE> ride) {
     constexpr int ES = F8 ? 1 : 2;                // operand element bytes
     constexpr int KT = 128 / ES;                  // elements per K-tile (one 128-byte LDS row)
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     AIM_LDS char* smem = (AIM_LDS char*)smem_raw;
+    int gemm_wgs = (int)gridDim.x;
+    if constexpr (RIDE) {
+        gemm_wgs = ride.gemm_wgs;
+        if ((int)blockIdx.x >= gemm_wgs) {
+            wgrad_tile::run_job(smem, ride.job, (int)blockIdx.x - gemm_wgs);
+            return;
+        }
+    }
     AIM_LDS char* escr = smem + 2 * BUF;          // epilogue scratch lives beside the K-loop images
 
     const int tiles_n = (g.N + 255) >> 8;
@@ -108,10 +136,10 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs g, int ntiles, in
     // workgroups of an XCD take CONTIGUOUS ranks, so at any moment an XCD's CUs work on neighbouring tiles of the row-major
     // tile sequence (shared A rows / W columns in their L2):  tile = rank + i * gridDim.x.  (Column groups per XCD -- a
     // weight slice resident in each L2 -- were measured twice and removed: the re-fetched weights are Infinity-Cache hits.)
-    const int rank = (gridDim.x & 7) == 0 ? (int)(blockIdx.x & 7) * (int)(gridDim.x >> 3) + (int)(blockIdx.x >> 3)
-                                          : xcd_remap((int)blockIdx.x, (int)gridDim.x);
+    const int rank = (gemm_wgs & 7) == 0 ? (int)(blockIdx.x & 7) * (gemm_wgs >> 3) + (int)(blockIdx.x >> 3)
+                                         : xcd_remap((int)blockIdx.x, gemm_wgs);
     const int tiles_m1 = (g.M + 255) >> 8;
-    const int wg_per_group = (int)gridDim.x;
+    const int wg_per_group = gemm_wgs;
     const int nseq = ntiles;
     auto seq_tile = [&](int seq) {
         if (seq >= ntiles) return ntiles;
@@ -387,7 +415,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs g, int ntiles, in
         else
             wave_epilogue<EPI, F8>(g, acc, escr + wave * EPI_SCRATCH, cur.m0 + wm * 128, cur.n0 + wn * 64, lane);
         if (probe) {        // diagnostics (aim_gemm_args.probe): per-tile timestamps of wave 0, 100 MHz ticks
-            const int slot = probe_i * (int)gridDim.x + (int)blockIdx.x;
+            const int slot = probe_i * gemm_wgs + (int)blockIdx.x;
             if (tid == 0 && slot < probe_cap) {
                 probe[slot * 4 + 0] = (unsigned long long)blockIdx.x | ((tc1 - tc0) << 16);   // K-loop shader cycles
                 probe[slot * 4 + 1] = tp0;
@@ -409,32 +437,48 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs g, int ntiles, in
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // drain the zero-fill stages of the tail
 }
 
-template <int EPI, bool F8 = false>
-int launch256(const GemmArgs& g, int nbatch, hipStream_t st) {
+// The persistent grid of a problem of `tiles` tiles on this device with `reserve` CUs kept out: one workgroup per CU, or --
+// balanced -- the fewest workgroups that still finish in ceil(tiles / cus) rounds.  1 182 tiles take 5 rounds on 256 CUs and
+// on 237.  The 19 CUs that would idle through the last round idle for the whole launch instead: a kernel of ANOTHER stream
+// does not get them (the dispatcher places a workgroup in its own shader engine, in order, and the holes sit in the last
+// engines: DESIGN.md section 4, "Streams"), but workgroups of THIS launch do -- the riders (aim_wgrad_ride_plan below).
+static int balanced_grid(int tiles, int reserve, int* rounds_out, int* spare_out) {
+    const int ncu = aim_device_cus();
+    const int cus = ncu - reserve > 8 ? ncu - reserve : 8;
+    int grid = tiles < cus ? tiles : cus;
+    int rounds = 1;
+    static const bool balanced = [] { const char* e = getenv("AIM_GEMM_BALANCED"); return !e || atoi(e) != 0; }();
+    if (tiles > cus) {
+        rounds = (tiles + cus - 1) / cus;
+        const int need = (tiles + rounds - 1) / rounds;
+        if (balanced && need < grid) grid = need;       // any size: without a multiple of 8 the kernel ranks its blocks by xcd_remap
+    }
+    if (rounds_out) *rounds_out = rounds;
+    if (spare_out) *spare_out = cus - grid > 0 ? cus - grid : 0;
+    return grid;
+}
+
+template <int EPI, bool F8 = false, bool RIDE = false>
+int launch256(const GemmArgs& g, int nbatch, hipStream_t st, const wgrad_tile::Job* job = nullptr, int ride_wgs = 0) {
     static bool attr_set = false;
     if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)gemm256_kernel<EPI, F8>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+        (void)hipFuncSetAttribute((const void*)gemm256_kernel<EPI, F8, RIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
         attr_set = true;
     }
     const int tiles = ((g.M + 255) / 256) * ((g.N + 255) / 256) * nbatch;
     // a persistent grid that fills every CU starves whatever runs beside it on another stream: the caller can keep a few
-    // CUs out of the grid while such work is in flight
-    const int reserve = g.reserve_cus > 0 ? g.reserve_cus : 0;       // per-call knob (aim_gemm_args.reserve_cus)
-    const int ncu = aim_device_cus();
-    const int cus = ncu - reserve > 8 ? ncu - reserve : 8;
-    int grid = tiles < cus ? tiles : cus;
-    // balanced grid: the fewest workgroups that still finish in ceil(tiles / cus) rounds.  1 182 tiles take 5 rounds on 256
-    // CUs and on 237: the 19 CUs that would idle through the last round are free for the other streams for the whole
-    // launch instead.
-    static const bool balanced = [] { const char* e = getenv("AIM_GEMM_BALANCED"); return !e || atoi(e) != 0; }();
-    if (balanced && tiles > cus) {
-        const int rounds = (tiles + cus - 1) / cus;
-        const int need = (tiles + rounds - 1) / rounds;
-        if (need < grid) grid = need;       // any size: without a multiple of 8 the kernel ranks its blocks by xcd_remap
-    }
+    // CUs out of the grid while such work is in flight (aim_gemm_args.reserve_cus)
+    const int grid = balanced_grid(tiles, g.reserve_cus > 0 ? g.reserve_cus : 0, nullptr, nullptr);
     static const int phase_skew = [] { const char* e = getenv("AIM_GEMM_SKEW"); return e ? atoi(e) : 1; }();
-    hipLaunchKernelGGL((gemm256_kernel<EPI, F8>), dim3(grid), dim3(512), LDS_BYTES, st, g, tiles, nbatch, phase_skew,
-                       (unsigned long long*)g.probe, g.probe ? g.probe_cap : 0);
+    RideArg<RIDE> ride;
+    int wgs = grid;
+    if constexpr (RIDE) {
+        ride.job = *job;
+        ride.gemm_wgs = grid;
+        wgs = grid + ride_wgs;
+    }
+    hipLaunchKernelGGL((gemm256_kernel<EPI, F8, RIDE>), dim3(wgs), dim3(512), LDS_BYTES, st, g, tiles, nbatch, phase_skew,
+                       (unsigned long long*)g.probe, g.probe ? g.probe_cap : 0, ride);
     AIM_CHECK_LAUNCH("aim_gemm_bf16(256)");
     return 0;
 }
@@ -464,4 +508,78 @@ int aim_gemm256_launch(const GemmArgs& g, int epi, int nbatch, hipStream_t st) {
     }
     aim_set_error("gemm256: unsupported epilogue %d", epi);
     return 1;
+}
+
+// ---- rider workgroups: an adapter weight gradient in the CUs the balanced grid leaves idle -----------------------------------
+// Chunks of a row range: at most max_chunks chunks of whole 32-row steps; returns the number of non-empty chunks.
+int aim_wgrad_range_chunks(int rows, int max_chunks, int* chunk_out) {
+    const int steps = (rows + wgrad_tile::MSTEP - 1) / wgrad_tile::MSTEP;
+    if (max_chunks < 1) max_chunks = 1;
+    const int chunk = ((steps + max_chunks - 1) / max_chunks) * wgrad_tile::MSTEP;
+    if (chunk_out) *chunk_out = chunk;
+    return rows > 0 ? (rows + chunk - 1) / chunk : 0;
+}
+
+int aim_gemm256_ride_launch(const GemmArgs& g, int epi, const aim_wgrad_ride_args& r, int* chunks_written, hipStream_t st) {
+    AIM_CHECK_ARG((long long)256 * g.lda * 2 < 0x7fffffffLL && (long long)256 * g.ldw * 2 < 0x7fffffffLL, "gemm256: leading dimension too large");
+    AIM_CHECK_ARG(epi == EPI_BF16 || epi == EPI_DACT, "gemm_ride: riders are hosted by the BF16 and DACT epilogues only (epilogue %d)", epi);
+    AIM_CHECK_ARG(r.G && r.A && r.slabs, "gemm_ride: null pointer");
+    AIM_CHECK_ARG(r.Nw > 0 && r.Kw > 0 && (r.Nw % 8) == 0 && (r.Kw % 8) == 0, "gemm_ride: Nw/Kw must be positive multiples of 8 (Nw=%d Kw=%d)", r.Nw, r.Kw);
+    AIM_CHECK_ARG((r.ldg % 8) == 0 && (r.lda % 8) == 0 && r.ldg >= r.Nw && r.lda >= r.Kw, "gemm_ride: ldg/lda must be multiples of 8 and cover a row");
+    AIM_CHECK_ARG(r.m_begin >= 0 && r.m_end > r.m_begin && r.chunks >= 1, "gemm_ride: empty row range or no chunks");
+    AIM_CHECK_ARG(!r.at || (r.bias_slabs && r.ntok > 0 && r.ntok * 4 <= RIDE_AT_BYTES),
+                  "gemm_ride: row factors need bias slabs and 0 < ntok <= %d", (RIDE_AT_BYTES) / 4);
+    int chunk = 0;
+    const int nchunks = aim_wgrad_range_chunks(r.m_end - r.m_begin, r.chunks, &chunk);
+    AIM_CHECK_ARG((long long)chunk * (r.ldg > r.lda ? r.ldg : r.lda) * 2 < 0x7fffffffLL, "gemm_ride: chunk too large");
+    const int tiles = ((r.Nw + wgrad_tile::TILE - 1) / wgrad_tile::TILE) * ((r.Kw + wgrad_tile::TILE - 1) / wgrad_tile::TILE);
+    wgrad_tile::Job job;
+    job.G = (const bf16_t*)r.G;
+    job.A = (const bf16_t*)r.A;
+    job.slabs = r.slabs;
+    job.bias_slabs = r.bias_slabs;
+    job.at = r.at;
+    job.ldg = r.ldg, job.lda = r.lda, job.Nw = r.Nw, job.Kw = r.Kw;
+    job.m_begin = r.m_begin, job.m_end = r.m_end, job.chunk = chunk, job.ntok = r.ntok;
+    if (chunks_written) *chunks_written = nchunks;
+    // (riders of empty chunks are not launched: the real chunk count sizes the grid)
+    if (epi == EPI_BF16) return launch256<EPI_BF16, false, true>(g, 1, st, &job, tiles * nchunks);
+    return launch256<EPI_DACT, false, true>(g, 1, st, &job, tiles * nchunks);
+}
+
+// Policy.  A host launch takes riders when its balanced grid leaves at least one spare CU per output tile of the gradient, and
+// gives each rider no more 32-row steps than it can finish before the host's own workgroups do:
+//     steps per rider <= c x tile rounds x (K-steps of a host tile + its epilogue in K-step times: 3 BF16, 8 DACT),
+// c = time of a host K-step / time of a rider step beside it.  Measured on the flagship shapes: a host
+// K-step 1.45 us, a rider step beside the host 1.15 us (0.86 alone), ratio 1.26; launch time against rider steps is flat up to
+// 504 (DACT, 21 rounds x 12) and 255..382 (K = 3 264 dgrad, 5 rounds x 51) steps per rider and grows behind.  The default
+// holds a fifth back: a host that gets longer costs the main stream, a row left over only the detached one.
+// AIM_WGRAD_RIDE_C overrides.  (The DACT launch is slowed by its riders -- 25 us of 550, HBM contention with its epilogue -- and
+// still wins in the whole step: AIM_WGRAD_RIDE_DACT=0 keeps riders off it, the A/B switch.)  A gradient none of whose rows rode yet is only started when this host covers at least half
+// of it: a launch that takes a fraction (ViT-L/14's DACT: 4 riders x 26 880 of 131 584 rows) leaves the stand-alone launch
+// nearly as long as it was and adds a second set of slabs.  Depends on shapes, the CU count and AIM_WGRAD_RIDE only.
+int aim_gemm256_ride_plan(const GemmArgs& g, int epi, int Nw, int Kw, int ntok, int M_total, int rows_left, int* chunks, int* rows) {
+    *chunks = 0;
+    *rows = 0;
+    static const bool on = [] { const char* e = getenv("AIM_WGRAD_RIDE"); return !e || atoi(e) != 0; }();
+    static const double c = [] { const char* e = getenv("AIM_WGRAD_RIDE_C"); const double v = e ? atof(e) : 0.0; return v > 0.0 ? v : AIM_WGRAD_RIDE_C_DEFAULT; }();
+    if (!on || rows_left <= 0 || ntok * 4 > RIDE_AT_BYTES) return 0;
+    const int tiles = ((g.M + 255) / 256) * ((g.N + 255) / 256);
+    int rounds = 1, spare = 0;
+    balanced_grid(tiles, g.reserve_cus > 0 ? g.reserve_cus : 0, &rounds, &spare);
+    const int wtiles = ((Nw + wgrad_tile::TILE - 1) / wgrad_tile::TILE) * ((Kw + wgrad_tile::TILE - 1) / wgrad_tile::TILE);
+    if (spare < wtiles) return 0;
+    static const bool dact_hosts = [] { const char* e = getenv("AIM_WGRAD_RIDE_DACT"); return !e || atoi(e) != 0; }();
+    if (epi == EPI_DACT && !dact_hosts) return 0;
+    const int steps = (int)(c * rounds * ((g.K + 63) / 64 + (epi == EPI_DACT ? 8 : 3)));
+    if (steps < 16) return 0;               // a rider's slab store and ring fill would outweigh its steps
+    int nch = spare / wtiles;
+    const int need = (rows_left + steps * wgrad_tile::MSTEP - 1) / (steps * wgrad_tile::MSTEP);
+    if (nch > need) nch = need;
+    long long take = (long long)nch * steps * wgrad_tile::MSTEP;
+    if (take > rows_left) take = rows_left;
+    if (rows_left == M_total && take * 2 < M_total) return 0;
+    *chunks = nch;
+    *rows = (int)take;
+    return 0;
 }

@@ -12,185 +12,33 @@
 #include "aim_common.h"
 #include <stdlib.h>
 #include "aim_kernels_internal.h"
+#include "wgrad_tile.h"
 
 namespace {
 
-constexpr int MSTEP = 32;                 // reduction rows per stage
-constexpr int NST = 4;                    // LDS ring depth: three stages in flight hide the HBM latency
-constexpr int IMG = MSTEP * 128;          // one [32 m][64 col] image = 4 KiB
-constexpr int OPER_BYTES = 4 * IMG;       // [32 m][256 col] = four images = 16 KiB
-constexpr int STAGE_BYTES = 2 * OPER_BYTES;
-constexpr int TILE = 256;                 // output tile 256 (n) x 256 (k)
+using wgrad_tile::MSTEP;
+using wgrad_tile::NST;
+using wgrad_tile::STAGE_BYTES;
+using wgrad_tile::TILE;
 
-// One workgroup = 8 waves as 2 (n) x 4 (k); a wave owns 128 x 64 outputs = 8 x 4 MFMA 16x16x32 tiles.
-// The kernel is bound by the bytes a CU can pull per cycle (every output tile re-reads its M-chunk of G and
-// A), so the tile is as large as the accumulators allow: [768 x 192] needs 3 tiles, 271 MB of operand reads
-// for M = 100 864 instead of 620 MB with 128 x 128 tiles.
-//
-// Bias gradient in the same pass (db != nullptr): db[n] += sum_m rs(m) G[m][n], rs(m) = at[m % ntok] (1 without `at`).  The
-// workgroups of the first k-tile column (tk == 0) already hold every G row of their chunk in LDS: thread t sums column
-// t & 255 over rows 16 (t >> 8) .. +15 of each stage beside the MFMAs (the kernel is bound by the CU's load path, not by LDS
-// or VALU issue); the per-chunk column sums go to their own slab and are added up, in chunk order, by the finish kernel.
-// This replaces a separate column-sum launch that re-read all of G from HBM (155 MB for the MLP_Adapter's D_fc2 bias).
+// One workgroup = one output tile x one M-chunk (wgrad_tile.h holds the body: the rider workgroups of the persistent GEMM
+// run the same function).  row0: the row of the whole problem that G / A row 0 is (the `at` factors are at[(row0 + m) % ntok]).
 __global__ __launch_bounds__(512) void wgrad_kernel(const bf16_t* __restrict__ G, int ldg, const bf16_t* __restrict__ A,
                                                     int lda, float* __restrict__ dW, int lddw, float* __restrict__ partial,
                                                     int M, int Nw, int Kw, int chunk, float* __restrict__ db,
-                                                    float* __restrict__ bias_partial, const float* __restrict__ at, int ntok) {
+                                                    float* __restrict__ bias_partial, const float* __restrict__ at, int ntok,
+                                                    int row0) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     AIM_LDS char* smem = (AIM_LDS char*)smem_raw;
-    AIM_LDS float* sAt = (AIM_LDS float*)(smem + NST * STAGE_BYTES);     // [ntok] row factors (only with `at`)
     const int tiles_k = (Kw + TILE - 1) / TILE;
     const int tiles = ((Nw + TILE - 1) / TILE) * tiles_k;
     const int cidx = blockIdx.x / tiles, tix = blockIdx.x - cidx * tiles;
     const int tn = tix / tiles_k, tk = tix - tn * tiles_k;
-    const int n0 = tn * TILE, k0 = tk * TILE;
     const int mbeg = cidx * chunk;
     const int mend = min(M, mbeg + chunk);
     if (mbeg >= mend) return;
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wn = wave >> 2, wk = wave & 3;
-    const int frow = lane & 15, fq = lane >> 4;
-
-    const bf16_t* Gb = G + (long long)mbeg * ldg + n0;
-    const bf16_t* Ab = A + (long long)mbeg * lda + k0;
-    const int rows = mend - mbeg;
-    aim_rsrc_words rG = make_rsrc_words(Gb, ((long long)(rows - 1) * ldg + min(TILE, Nw - n0)) * 2);
-    aim_rsrc_words rA = make_rsrc_words(Ab, ((long long)(rows - 1) * lda + min(TILE, Kw - k0)) * 2);
-
-    // staging: per operand 16 pieces (4 column images x 4 row groups of 8); a wave takes 2 of each.  A piece's offset is its
-    // stage-0 offset plus ms * (32 rows): one v_add per piece and step.  Rows past the chunk need no test -- the resources end
-    // with the chunk's last row, so their offsets are out of range by themselves (zero fill); columns past Nw / Kw carry
-    // AIM_OOB from the start (AIM_OOB + ms * step stays out of range).
-    const int srow = lane >> 3, schunk = (lane & 7) ^ srow;
-    unsigned vg0[2], va0[2];
-    AIM_LDS char* pdst[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int piece = wave * 2 + j;           // 0..15
-        const int img = piece >> 2, rg = piece & 3;
-        const int r = rg * 8 + srow;              // row inside stage 0
-        const int col = img * 64 + schunk * 8;
-        vg0[j] = n0 + col < Nw ? (unsigned)((r * ldg + col) * 2) : AIM_OOB;
-        va0[j] = k0 + col < Kw ? (unsigned)((r * lda + col) * 2) : AIM_OOB;
-        pdst[j] = smem + img * IMG + rg * 1024;
-    }
-    const unsigned gstep = (unsigned)(MSTEP * ldg * 2), astep = (unsigned)(MSTEP * lda * 2);
-    auto stage = [&](int buf, int ms) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            stage_piece_asm(rG, pdst[j] + buf * STAGE_BYTES, vg0[j] + (unsigned)ms * gstep);
-            stage_piece_asm(rA, pdst[j] + buf * STAGE_BYTES + OPER_BYTES, va0[j] + (unsigned)ms * astep);
-        }
-    };
-
-    f32x4 acc[8][4];
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    // transposing fragment read: 16 columns c0..c0+15 of the operand's [32 m][256] stage, reduction rows
-    // {4*fq + 0..3} and {16 + 4*fq + 0..3}; lane i = lane&15 supplies row (i>>2), cols 4*(i&3)..
-    auto frag = [&](const AIM_LDS char* oper, int c0) -> bf16x8 {
-        const AIM_LDS char* img = oper + (c0 >> 6) * IMG;
-        const int ch = ((c0 & 63) >> 3) + ((frow & 3) >> 1), half8 = (frow & 1) * 8;
-        const int r0 = fq * 4 + (frow >> 2);
-        const bf16x4 a = lds_read_tr4(img + swz_off(r0, ch) + half8);
-        const bf16x4 b = lds_read_tr4(img + swz_off(r0 + 16, ch) + half8);
-        bf16x8 f;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            f[e] = a[e];
-            f[4 + e] = b[e];
-        }
-        return f;
-    };
-
-    // ring of NST stages; each wave issues 4 LDS-DMA loads per stage.  Iteration ms: vmcnt(8) retires
-    // stage ms (stages ms+1, ms+2 stay in flight), one barrier, re-stage buffer (ms+3)%4 -- read in
-    // iteration ms-1, which every wave finished before this barrier -- then 24 tr-reads + 32 MFMA.
-    const int nsteps = (rows + MSTEP - 1) / MSTEP;
-    const bool do_bias = db != nullptr && tk == 0;      // workgroup-uniform
-    // bias column sums: thread t owns the 8 columns of 16-byte chunk (t & 31) in rows (t >> 5) and (t >> 5) + 16 of every stage
-    // (two ds_read_b128 per step; the first version read sixteen 2-byte values per thread and step: +30 us per launch)
-    float bs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    const int bcg = tid & 31, brow = tid >> 5;
-    int btok0 = 0, btok1 = 0;
-    if (do_bias && at) {
-        for (int i = tid; i < ntok; i += 512) sAt[i] = at[i];
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // written before the loop's first barrier publishes it
-        btok0 = (mbeg + brow) % ntok;
-        btok1 = (mbeg + brow + 16) % ntok;
-    }
-    const int bstep = MSTEP % (ntok > 0 ? ntok : 1);
-    stage(0, 0); stage(1, 1); stage(2, 2);            // stages past the chunk are zero-fill, still counted
-    for (int ms = 0; ms < nsteps; ++ms) {
-        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        stage((ms + 3) % NST, ms + 3);
-        const AIM_LDS char* sG = smem + (ms % NST) * STAGE_BYTES;
-        const AIM_LDS char* sA = sG + OPER_BYTES;
-        if (do_bias) {
-            // chunk bcg of the [32 m][256 n] stage: image bcg >> 3, 16-byte chunk bcg & 7 of rows brow and brow + 16
-            const AIM_LDS char* img = sG + (bcg >> 3) * IMG;
-            const bf16x8 v0 = lds_read8(img + swz_off(brow, bcg & 7));
-            const bf16x8 v1 = lds_read8(img + swz_off(brow + 16, bcg & 7));
-            float f0 = 1.0f, f1 = 1.0f;
-            if (at) {
-                f0 = sAt[btok0];
-                f1 = sAt[btok1];
-                btok0 += bstep; if (btok0 >= ntok) btok0 -= ntok;
-                btok1 += bstep; if (btok1 >= ntok) btok1 -= ntok;
-            }
-#pragma unroll
-            for (int e = 0; e < 8; ++e) bs[e] += f0 * (float)v0[e] + f1 * (float)v1[e];      // rows past the chunk are zero-filled
-        }
-        bf16x8 gf[8], af[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) af[j] = frag(sA, wk * 64 + j * 16);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) gf[i] = frag(sG, wn * 128 + i * 16);
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[j], gf[i], acc[i][j], 0, 0, 0);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (do_bias) {          // the sixteen row groups of a column meet in LDS (the stage images are dead now), summed in order
-        __syncthreads();
-        AIM_LDS float* red = (AIM_LDS float*)smem;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) red[brow * 256 + bcg * 8 + e] = bs[e];
-        __syncthreads();
-        if (tid < 256 && n0 + tid < Nw) {
-            float v = 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) v += red[r * 256 + tid];
-            if (bias_partial) bias_partial[(long long)cidx * Nw + n0 + tid] = v;
-            else db[n0 + tid] += v;                    // one chunk: this workgroup is the column's only writer
-        }
-    }
-    // The MFMA is issued with the A fragment FIRST (D[k][n]): the lane holds n = .. + (lane & 15) and the four consecutive
-    // k = .. + 4 * (lane >> 4) + e, so a partial tile leaves as 16-byte stores (32 per wave; the 4-byte form, 128 per wave,
-    // took 7.6 us of a 46 us workgroup).
-    // With a scratch slab the chunk's partial tile is stored plainly (slab [chunk][Nw][Kw], summed by
-    // wgrad_finish_kernel: no atomics, bitwise reproducible); otherwise fp32 atomics into dW.
-    float* slab = partial ? partial + (long long)cidx * Nw * Kw : nullptr;
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int n = n0 + wn * 128 + i * 16 + frow;
-            const int k = k0 + wk * 64 + j * 16 + fq * 4;
-            if (n >= Nw || k >= Kw) continue;          // Kw is a multiple of 8: a lane's four k are in range together
-            if (slab) *(f32x4*)(slab + (long long)n * Kw + k) = acc[i][j];
-            else
-#pragma unroll
-                for (int e = 0; e < 4; ++e) atomicAdd(dW + (long long)n * lddw + k + e, acc[i][j][e]);
-        }
+    wgrad_tile::run<false>(smem, G, ldg, A, lda, dW, lddw, partial ? partial + (long long)cidx * Nw * Kw : nullptr, Nw, Kw, tn, tk,
+                           mbeg, mend, row0, db != nullptr, db, bias_partial ? bias_partial + (long long)cidx * Nw : nullptr, at, ntok);
 }
 
 // dW[n][k] += sum_c slab[c][n][k]  and  db[n] += sum_c bias_slab[c][n], both in chunk order (bitwise reproducible).
@@ -287,7 +135,7 @@ extern "C" int aim_wgrad_bias_bf16(const aim_bf16* G, int ldg, const aim_bf16* A
         db = nullptr;
     }
     hipLaunchKernelGGL(wgrad_kernel, dim3(tiles * nchunks), dim3(512), lds_bytes, (hipStream_t)stream,
-                       (const bf16_t*)G, ldg, (const bf16_t*)A, lda, dW, lddw, slab, M, Nw, Kw, chunk, db, bias_slab, at, ntok);
+                       (const bf16_t*)G, ldg, (const bf16_t*)A, lda, dW, lddw, slab, M, Nw, Kw, chunk, db, bias_slab, at, ntok, 0);
     AIM_CHECK_LAUNCH("aim_wgrad_bf16");
     if (slab) {
         const long long total = (long long)Nw * Kw;
@@ -307,4 +155,50 @@ extern "C" int aim_wgrad_bias_bf16(const aim_bf16* G, int ldg, const aim_bf16* A
 extern "C" int aim_wgrad_bf16(const aim_bf16* G, int ldg, const aim_bf16* A, int lda, float* dW, int lddw, float* db,
                               int M, int Nw, int Kw, float* workspace, int64_t workspace_bytes, void* stream) {
     return aim_wgrad_bias_bf16(G, ldg, A, lda, dW, lddw, db, nullptr, 0, M, Nw, Kw, workspace, workspace_bytes, stream);
+}
+
+static void wgrad_attr() {
+    static bool attr_set = false;
+    if (!attr_set) {
+        (void)hipFuncSetAttribute((const void*)wgrad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        attr_set = true;
+    }
+}
+
+extern "C" int aim_wgrad_slabs_bf16(const aim_bf16* G, int ldg, const aim_bf16* A, int lda, const float* at, int ntok, int m_begin,
+                                    int m_end, int Nw, int Kw, float* slabs, float* bias_slabs, int max_chunks, int* chunks_written,
+                                    void* stream) {
+    AIM_CHECK_ARG(Nw > 0 && Kw > 0 && (Nw % 8) == 0 && (Kw % 8) == 0, "wgrad_slabs: Nw/Kw must be positive multiples of 8 (Nw=%d Kw=%d)", Nw, Kw);
+    AIM_CHECK_ARG((ldg % 8) == 0 && (lda % 8) == 0, "wgrad_slabs: ldg/lda must be multiples of 8");
+    AIM_CHECK_ARG(G && A && slabs && chunks_written, "wgrad_slabs: null pointer");
+    AIM_CHECK_ARG(m_begin >= 0 && m_end > m_begin, "wgrad_slabs: empty row range [%d, %d)", m_begin, m_end);
+    AIM_CHECK_ARG(!at || (bias_slabs && ntok > 0 && ntok <= 4096), "wgrad_slabs: row factors need bias slabs and 0 < ntok <= 4096");
+    const int rows = m_end - m_begin;
+    const int tiles = ((Nw + TILE - 1) / TILE) * ((Kw + TILE - 1) / TILE);
+    int chunk = 0;
+    const int nchunks = max_chunks > 0 ? aim_wgrad_range_chunks(rows, max_chunks, &chunk) : wgrad_chunks(rows, tiles, &chunk);
+    AIM_CHECK_ARG((long long)chunk * (ldg > lda ? ldg : lda) * 2 < 0x7fffffffLL, "wgrad_slabs: chunk too large");
+    wgrad_attr();
+    const int lds_bytes = NST * STAGE_BYTES + (at ? ((ntok * 4 + 15) & ~15) : 0);
+    // db only says "sum the bias columns": with a bias slab the kernel never touches it
+    hipLaunchKernelGGL(wgrad_kernel, dim3(tiles * nchunks), dim3(512), lds_bytes, (hipStream_t)stream,
+                       (const bf16_t*)G + (long long)m_begin * ldg, ldg, (const bf16_t*)A + (long long)m_begin * lda, lda,
+                       (float*)nullptr, 0, slabs, rows, Nw, Kw, chunk, bias_slabs, bias_slabs, at, ntok, m_begin);
+    AIM_CHECK_LAUNCH("aim_wgrad_slabs_bf16");
+    *chunks_written = nchunks;
+    return 0;
+}
+
+extern "C" int aim_wgrad_finish(const float* slabs, const float* bias_slabs, int nchunks, float* dW, int lddw, float* db, int Nw,
+                                int Kw, void* stream) {
+    AIM_CHECK_ARG(slabs && dW && nchunks > 0, "wgrad_finish: null pointer or no slabs");
+    AIM_CHECK_ARG(Nw > 0 && Kw > 0 && (Nw % 8) == 0 && (Kw % 8) == 0 && (lddw % 4) == 0, "wgrad_finish: Nw/Kw multiples of 8, lddw of 4");
+    AIM_CHECK_ARG((bias_slabs != nullptr) == (db != nullptr), "wgrad_finish: bias slabs and db go together");
+    const long long total = (long long)Nw * Kw;
+    unsigned fgrid = (unsigned)((total / 4 + 255) / 256);
+    if (bias_slabs && (unsigned)((Nw + 3) / 4) > fgrid) fgrid = (unsigned)((Nw + 3) / 4);
+    hipLaunchKernelGGL(wgrad_finish_kernel, dim3(fgrid), dim3(256), 0, (hipStream_t)stream, slabs, dW, lddw, nchunks, Nw, Kw,
+                       bias_slabs, db);
+    AIM_CHECK_LAUNCH("aim_wgrad_finish");
+    return 0;
 }

@@ -35,6 +35,15 @@ class GemmArgs(Structure):
     ]
 
 
+class WgradRideArgs(Structure):
+    """Mirror of ``aim_wgrad_ride_args``."""
+    _fields_ = [
+        ("G", c_void_p), ("A", c_void_p), ("ldg", c_int32), ("lda", c_int32), ("Nw", c_int32), ("Kw", c_int32),
+        ("m_begin", c_int32), ("m_end", c_int32), ("at", c_void_p), ("ntok", c_int32), ("chunks", c_int32),
+        ("slabs", c_void_p), ("bias_slabs", c_void_p),
+    ]
+
+
 P = c_void_p
 I = c_int
 L = c_int64
@@ -50,6 +59,10 @@ SIGNATURES = {
     "aim_wgrad_bf16": [P, I, P, I, P, I, P, I, I, I, P, L, P],
     "aim_wgrad_workspace_bytes": [I, I, I],
     "aim_wgrad_bias_bf16": [P, I, P, I, P, I, P, P, I, I, I, I, P, L, P],
+    "aim_wgrad_slabs_bf16": [P, I, P, I, P, I, I, I, I, I, P, P, I, POINTER(c_int), P],
+    "aim_wgrad_finish": [P, P, I, P, I, P, I, I, P],
+    "aim_gemm_bf16_ride": [POINTER(GemmArgs), I, POINTER(WgradRideArgs), POINTER(c_int), P],
+    "aim_wgrad_ride_plan": [POINTER(GemmArgs), I, I, I, I, I, I, POINTER(c_int), POINTER(c_int)],
     "aim_layernorm_fwd": [P, L, P, P, P, P, L, P, P, I, I, F, P],
     "aim_layernorm_fwd_fp8": [P, L, P, P, P, L, I, I, F, P],
     "aim_layernorm_fwd_x16": [P, L, P, P, P, P, P, L, I, I, F, P],
@@ -115,7 +128,7 @@ SIGNATURES = {
     "aim_layernorm_gb_bwd": [P, I, L, P, L, P, P, P, P, I, I, P, L, P],
 }
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 
 def load_library():

@@ -3,12 +3,12 @@
 PyTorch is used for device memory and streams only; every function here launches exactly the HIP
 kernel(s) of the same name on the current stream and returns without synchronising.
 """
-from ctypes import byref
+from ctypes import byref, c_int
 from typing import Optional
 
 import torch
 
-from .lib import GemmArgs, check, load_library
+from .lib import GemmArgs, WgradRideArgs, check, load_library
 
 EPI_BF16, EPI_ACT, EPI_DACT, EPI_F32, EPI_EXPSUM, EPI_ACT8, EPI_RES16 = 0, 1, 2, 3, 4, 5, 6
 FP8 = torch.float8_e4m3fn          # OCP e4m3 (gfx950); stored as bytes
@@ -89,8 +89,10 @@ def gemm(a: torch.Tensor, w: torch.Tensor, epi: int, out: torch.Tensor, *, bias=
          stride_w: int = 0, M: Optional[int] = None, N: Optional[int] = None, K: Optional[int] = None,
          lda: Optional[int] = None, ldw: Optional[int] = None, ldv: Optional[int] = None, n_split: int = 0,
          act2: int = 0, xrow=None, reserve_cus: int = 0, probe=None, aux_grad: bool = False, aux_frag: bool = False,
-         slot_stride: int = 0, small_tile: bool = False):
-    """``out = epilogue(a @ w.T)``; ``a`` is ``[M, K]`` (row stride ``lda``), ``w`` is ``[N, K]``."""
+         slot_stride: int = 0, small_tile: bool = False, ride=None):
+    """``out = epilogue(a @ w.T)``; ``a`` is ``[M, K]`` (row stride ``lda``), ``w`` is ``[N, K]``.
+    ``ride``: a list of ``WgradRide`` objects -- the launch may carry rider workgroups for one of them, as the library's
+    policy decides -- or one ``ride_args(...)``: the launch carries exactly those riders (``.written`` = slabs filled)."""
     lib = load_library()
     _chk(a, BF16, "a"); _chk(w, BF16, "w")
     for n_, t_ in (("bias", bias), ("resid", resid), ("af", af), ("at", at), ("vec", vec), ("bt", bt)):
@@ -142,11 +144,117 @@ def gemm(a: torch.Tensor, w: torch.Tensor, epi: int, out: torch.Tensor, *, bias=
     if timed:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-    check(lib.aim_gemm_bf16(byref(g), epi, batch, _stream()), "aim_gemm_bf16")
+    if isinstance(ride, WgradRideArgs):
+        n = c_int(0)
+        check(lib.aim_gemm_bf16_ride(byref(g), epi, byref(ride), byref(n), _stream()), "aim_gemm_bf16_ride")
+        ride.written = n.value
+    elif not (ride and batch == 1 and _launch_with_riders(lib, g, epi, ride)):
+        check(lib.aim_gemm_bf16(byref(g), epi, batch, _stream()), "aim_gemm_bf16")
     if timed:
         e1.record()
         GEMM_TIMER.records.append((epi, 2.0 * g.M * g.N * g.K * batch, e0, e1))
     return out
+
+
+def ride_args(g, a, m_begin: int, m_end: int, chunks: int, slabs, bias_slabs=None, at=None, ntok: int = 0) -> WgradRideArgs:
+    """Riders for rows ``[m_begin, m_end)`` of ``sum_m g[m,n] a[m,k]`` in ``chunks`` row chunks per 256 x 256 tile; chunk c
+    goes to ``slabs[c]`` ([Nw, Kw] f32 each) and, with ``bias_slabs``, its ``at``-weighted column sums to ``bias_slabs[c]``."""
+    _chk(g, BF16, "g"); _chk(a, BF16, "a"); _chk(slabs, F32, "slabs"); _chk(bias_slabs, F32, "bias_slabs"); _chk(at, F32, "at")
+    assert g.shape[0] == a.shape[0] and 0 <= m_begin < m_end <= g.shape[0]
+    assert slabs.is_contiguous() and slabs.numel() >= chunks * g.shape[1] * a.shape[1]
+    assert bias_slabs is None or (bias_slabs.is_contiguous() and bias_slabs.numel() >= chunks * g.shape[1])
+    ra = WgradRideArgs()
+    ra.G, ra.A, ra.ldg, ra.lda = g.data_ptr(), a.data_ptr(), g.stride(0), a.stride(0)
+    ra.Nw, ra.Kw, ra.m_begin, ra.m_end = g.shape[1], a.shape[1], m_begin, m_end
+    ra.at, ra.ntok, ra.chunks = _p(at), ntok, chunks
+    ra.slabs, ra.bias_slabs = slabs.data_ptr(), _p(bias_slabs)
+    ra.keep = (g, a, slabs, bias_slabs, at)
+    return ra
+
+
+def wgrad_slabs(g, a, m_begin: int, m_end: int, slabs, bias_slabs=None, at=None, ntok: int = 0, max_chunks: int = 0) -> int:
+    """The stand-alone launch for rows ``[m_begin, m_end)``: partial sums into ``slabs`` / ``bias_slabs`` as the riders
+    write them; returns the number of slabs filled."""
+    _chk(g, BF16, "g"); _chk(a, BF16, "a"); _chk(slabs, F32, "slabs"); _chk(bias_slabs, F32, "bias_slabs"); _chk(at, F32, "at")
+    assert g.shape[0] == a.shape[0] and 0 <= m_begin < m_end <= g.shape[0] and slabs.is_contiguous()
+    assert bias_slabs is None or bias_slabs.is_contiguous()
+    n = c_int(0)
+    check(load_library().aim_wgrad_slabs_bf16(g.data_ptr(), g.stride(0), a.data_ptr(), a.stride(0), _p(at), ntok, m_begin, m_end,
+                                              g.shape[1], a.shape[1], slabs.data_ptr(), _p(bias_slabs), max_chunks, byref(n),
+                                              _stream()), "aim_wgrad_slabs_bf16")
+    return n.value
+
+
+def wgrad_finish(slabs, nchunks: int, dw, bias_slabs=None, db=None):
+    """``dw += sum_c slabs[c]`` and ``db += sum_c bias_slabs[c]`` over the first ``nchunks`` slabs, in that order."""
+    _chk(slabs, F32, "slabs"); _chk(bias_slabs, F32, "bias_slabs"); _chk(dw, F32, "dw"); _chk(db, F32, "db")
+    check(load_library().aim_wgrad_finish(slabs.data_ptr(), _p(bias_slabs), nchunks, dw.data_ptr(), dw.stride(0), _p(db),
+                                          dw.shape[0], dw.shape[1], _stream()), "aim_wgrad_finish")
+
+
+RIDE_STATS = {"launches": 0, "rows": 0}      # rider launches / rows they summed, since import (tests, diagnostics)
+
+
+class WgradRide:
+    """An adapter weight gradient ``dw[n,k] += sum_m g[m,n] a[m,k]`` (``db[n] += sum_m at[m % ntok] g[m,n]``) whose rows are
+    summed by rider workgroups of the GEMM launches it is offered to (``gemm(..., ride=[...])``: each takes the rows the
+    library's policy gives it, ``aim_wgrad_ride_plan``), the rest by a stand-alone launch in ``finish``.  All partial sums
+    lie in one workspace in row order and ``finish`` adds them up in that order: bitwise reproducible."""
+    CAP = 48          # slabs of the workspace (flagship: 4 + 6 + 6 + 6 riders' chunks and the remainder's)
+
+    def __init__(self, g, a, dw, db=None, at=None, ntok: int = 0):
+        _chk(g, BF16, "g"); _chk(a, BF16, "a"); _chk(dw, F32, "dw"); _chk(db, F32, "db"); _chk(at, F32, "at")
+        assert g.shape[0] == a.shape[0] and dw.shape == (g.shape[1], a.shape[1])
+        self.g, self.a, self.dw, self.db, self.at, self.ntok = g, a, dw, db, at, ntok
+        self.M, self.Nw, self.Kw = g.shape[0], g.shape[1], a.shape[1]
+        self.next_row = 0       # rows [0, next_row) have riders
+        self.used = 0           # slabs written
+        self.ws = None
+        self.open = True        # still offered to host launches
+
+    @property
+    def left(self) -> int:
+        return self.M - self.next_row
+
+    def _slabs(self):
+        """The slab views behind the ones already written."""
+        if self.ws is None:
+            self.ws = torch.empty(self.CAP * self.Nw * (self.Kw + 1), dtype=F32, device=self.g.device)
+        w = self.ws[:self.CAP * self.Nw * self.Kw].view(self.CAP, self.Nw, self.Kw)
+        b = self.ws[self.CAP * self.Nw * self.Kw:].view(self.CAP, self.Nw) if self.db is not None else None
+        return w, b
+
+    def finish(self):
+        """The rows no rider took (stand-alone launch into the slabs behind the riders'), then the sum of all slabs."""
+        assert self.used > 0
+        w, b = self._slabs()
+        if self.left > 0:
+            self.used += wgrad_slabs(self.g, self.a, self.next_row, self.M, w[self.used:], b[self.used:] if b is not None else None,
+                                     at=self.at, ntok=self.ntok, max_chunks=max(1, min(self.CAP - self.used, self.left // 1024)))
+            self.next_row = self.M
+        wgrad_finish(w, self.used, self.dw, b, self.db)
+        self.open = False
+
+
+def _launch_with_riders(lib, g: GemmArgs, epi: int, rides) -> bool:
+    """Offer the launch to the gradients with rows left, the one with the most first; True: launched (with riders)."""
+    for r in sorted((r for r in rides if r.open and r.left > 0), key=lambda r: -r.left):
+        chunks, rows = c_int(0), c_int(0)
+        check(lib.aim_wgrad_ride_plan(byref(g), epi, r.Nw, r.Kw, r.ntok if r.at is not None else 0, r.M, r.left,
+                                      byref(chunks), byref(rows)), "aim_wgrad_ride_plan")
+        if chunks.value <= 0 or r.used + chunks.value >= r.CAP:      # (one slab stays free for the remainder)
+            continue
+        w, b = r._slabs()
+        ra = ride_args(r.g, r.a, r.next_row, r.next_row + rows.value, chunks.value, w[r.used:], b[r.used:] if b is not None else None,
+                       at=r.at, ntok=r.ntok)
+        n = c_int(0)
+        check(lib.aim_gemm_bf16_ride(byref(g), epi, byref(ra), byref(n), _stream()), "aim_gemm_bf16_ride")
+        r.used += n.value
+        r.next_row += rows.value
+        RIDE_STATS["launches"] += 1
+        RIDE_STATS["rows"] += rows.value
+        return True
+    return False
 
 
 def gemm_fp8(a8: torch.Tensor, w8: torch.Tensor, wscale: torch.Tensor, epi: int, out: torch.Tensor, *, bias=None,

@@ -32,7 +32,7 @@ extern "C" {
 
 typedef uint16_t aim_bf16;
 
-#define AIM_ABI_VERSION 13
+#define AIM_ABI_VERSION 14
 
 int aim_version(void);                /* == AIM_ABI_VERSION */
 const char* aim_last_error(void);     /* message of the last failing call on this thread */
@@ -159,6 +159,43 @@ int64_t aim_wgrad_workspace_bytes(int M, int Nw, int Kw);
  * the MLP_Adapter's D_fc2 (vit_clip.py:286) is the user. */
 int aim_wgrad_bias_bf16(const aim_bf16* G, int ldg, const aim_bf16* A, int lda, float* dW, int lddw, float* db,
                         const float* at, int ntok, int M, int Nw, int Kw, float* workspace, int64_t workspace_bytes, void* stream);
+
+/* The two halves of aim_wgrad_bias_bf16 apart (ABI 14), for a gradient whose rows are summed by more than one launch:
+ * aim_wgrad_slabs_bf16 writes the partial sums of rows [m_begin, m_end) of the problem (G, A point at its row 0; the row
+ * factors are at[m % ntok] of that absolute row index) as at most max_chunks (<= 0: the library's choice) slabs
+ * slabs[c][Nw][Kw] and, with bias_slabs != NULL, bias_slabs[c][Nw]; *chunks_written = the slabs it filled.  aim_wgrad_finish
+ * adds nchunks consecutive slabs, in that order, into dW / db (bias_slabs, db NULL: weights only).  No atomics anywhere. */
+int aim_wgrad_slabs_bf16(const aim_bf16* G, int ldg, const aim_bf16* A, int lda, const float* at, int ntok, int m_begin,
+                         int m_end, int Nw, int Kw, float* slabs, float* bias_slabs, int max_chunks, int* chunks_written,
+                         void* stream);
+int aim_wgrad_finish(const float* slabs, const float* bias_slabs, int nchunks, float* dW, int lddw, float* db, int Nw, int Kw,
+                     void* stream);
+
+/* Rider workgroups (ABI 14; no reference counterpart -- scheduling).  The persistent large-tile GEMM sizes its grid so that
+ * the last tile round is full, which leaves CUs idle for the whole launch (1 182 tiles: 237 workgroups on 256 CUs).
+ * aim_gemm_bf16_ride is aim_gemm_bf16 (batch 1, AIM_EPI_BF16 or AIM_EPI_DACT, a problem the large-tile kernel runs in one
+ * launch) whose launch carries tiles(Nw, Kw) * chunks more workgroups; each sums one 256 x 256 tile of a weight gradient
+ * over one chunk of rows [m_begin, m_end) into slabs[c][Nw][Kw] (and bias_slabs[c][Nw]) as aim_wgrad_slabs_bf16 does;
+ * *chunks_written slabs are filled.  The GEMM's output has the bits of the launch without riders; riders and GEMM
+ * workgroups share nothing, a slab is complete when the launch is.  at needs bias_slabs and ntok <= 4096.
+ * aim_wgrad_ride_plan is the policy: how many chunks and rows (from rows_left of a gradient of M_total rows) this host
+ * launch should carry -- 0 / 0: none.  It depends on the shapes, the CU count, reserve_cus and AIM_WGRAD_RIDE (0: never)
+ * only; AIM_WGRAD_RIDE_C overrides the measured ratio of a host K-step's time to a rider step's, AIM_WGRAD_RIDE_DACT=0 keeps
+ * riders off AIM_EPI_DACT launches. */
+typedef struct aim_wgrad_ride_args {
+    const aim_bf16* G;      /* [M, ldg] gradient rows, row 0 of the whole problem                */
+    const aim_bf16* A;      /* [M, lda] activation rows                                          */
+    int32_t ldg, lda, Nw, Kw;
+    int32_t m_begin, m_end; /* the rows the riders sum                                           */
+    const float* at;        /* [ntok] bias row factor or NULL                                    */
+    int32_t ntok;
+    int32_t chunks;         /* row chunks per tile (riders = tiles * chunks; empty chunks are not launched) */
+    float* slabs;           /* [chunks][Nw][Kw]                                                  */
+    float* bias_slabs;      /* [chunks][Nw] or NULL: no bias gradient                            */
+} aim_wgrad_ride_args;
+int aim_gemm_bf16_ride(const aim_gemm_args* args, int epilogue, const aim_wgrad_ride_args* ride, int* chunks_written, void* stream);
+int aim_wgrad_ride_plan(const aim_gemm_args* host, int epilogue, int Nw, int Kw, int ntok, int M_total, int rows_left,
+                        int* chunks, int* rows);
 
 /* ------------------------------------------------------------------------------------------
  * LayerNorm (fp32 statistics, eps inside rsqrt) -- vit_clip.py:71-77 (ln_1, ln_2, ln_pre, ln_post)
