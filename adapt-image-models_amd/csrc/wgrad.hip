@@ -113,6 +113,7 @@ extern "C" int aim_wgrad_bias_bf16(const aim_bf16* G, int ldg, const aim_bf16* A
                                    void* stream) {
     AIM_CHECK_ARG(M > 0 && Nw > 0 && Kw > 0 && (Nw % 8) == 0 && (Kw % 8) == 0, "wgrad: Nw/Kw must be positive multiples of 8 (Nw=%d Kw=%d)", Nw, Kw);
     AIM_CHECK_ARG((ldg % 8) == 0 && (lda % 8) == 0 && (lddw % 4) == 0, "wgrad: ldg/lda must be multiples of 8, lddw of 4");
+    AIM_CHECK_ARG(ldg >= Nw && lda >= Kw && lddw >= Kw, "wgrad: ldg/lda/lddw must cover a row (ldg=%d lda=%d lddw=%d)", ldg, lda, lddw);
     AIM_CHECK_ARG(G && A && dW, "wgrad: null pointer");
     AIM_CHECK_ARG(!at || (db && ntok > 0 && ntok <= 4096), "wgrad: row factors need db and 0 < ntok <= 4096");
     const int tiles = ((Nw + TILE - 1) / TILE) * ((Kw + TILE - 1) / TILE);
@@ -170,6 +171,7 @@ extern "C" int aim_wgrad_slabs_bf16(const aim_bf16* G, int ldg, const aim_bf16* 
                                     void* stream) {
     AIM_CHECK_ARG(Nw > 0 && Kw > 0 && (Nw % 8) == 0 && (Kw % 8) == 0, "wgrad_slabs: Nw/Kw must be positive multiples of 8 (Nw=%d Kw=%d)", Nw, Kw);
     AIM_CHECK_ARG((ldg % 8) == 0 && (lda % 8) == 0, "wgrad_slabs: ldg/lda must be multiples of 8");
+    AIM_CHECK_ARG(ldg >= Nw && lda >= Kw, "wgrad_slabs: ldg/lda must cover a row (ldg=%d lda=%d)", ldg, lda);
     AIM_CHECK_ARG(G && A && slabs && chunks_written, "wgrad_slabs: null pointer");
     AIM_CHECK_ARG(m_begin >= 0 && m_end > m_begin, "wgrad_slabs: empty row range [%d, %d)", m_begin, m_end);
     AIM_CHECK_ARG(!at || (bias_slabs && ntok > 0 && ntok <= 4096), "wgrad_slabs: row factors need bias slabs and 0 < ntok <= 4096");

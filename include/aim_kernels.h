@@ -147,7 +147,9 @@ int aim_gemm_expsum_tiles(int M, int N);
  *   dW[n][k] += sum_m G[m][n] * A[m][k]      db[n] += sum_m G[m][n]
  * With a workspace the split-M partial slabs are summed in a fixed order by a second kernel (no atomics, bitwise
  * reproducible: the form the training step uses); workspace == NULL falls back to fp32 atomics.
- * autograd counterpart of Adapter.D_fc1 / D_fc2 (vit_clip.py:57-58).  Nw, Kw multiples of 8.
+ * autograd counterpart of Adapter.D_fc1 / D_fc2 (vit_clip.py:57-58).  Nw, Kw multiples of 8; ldg, lda multiples of 8 and
+ * lddw a multiple of 4, each at least a row long (ldg >= Nw, lda >= Kw, lddw >= Kw: anything else is refused, here and by
+ * aim_wgrad_slabs_bf16).
  * ------------------------------------------------------------------------------------------ */
 int aim_wgrad_bf16(const aim_bf16* G, int ldg, const aim_bf16* A, int lda, float* dW, int lddw,
                    float* db, int M, int Nw, int Kw,
