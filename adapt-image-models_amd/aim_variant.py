@@ -12,7 +12,9 @@ Same parameter names / shapes, same ``init_weights`` policy, same embedding and 
 (``vitclip_aim.py:468-493`` restates ``vit_clip.py:433-458``), so it subclasses it; only the block's forward and its
 hand-written backward differ.  Every GEMM here has M = B*T*N rows (persistent 256x256 kernel); the temporal attention is
 ``aim_tattn_fwd/bwd`` (csrc/tattn.hip), which reads the frame-major fused qkv buffer in place instead of rearranging the
-activations twice as the reference does.
+activations twice as the reference does.  A no-grad forward uses ``aim_tattn_fwd_infer`` (no stored probabilities, same bits),
+and with ``set_inference_precision('fp8')`` and at least 1024 token rows the block's six large GEMMs run on fp8 e4m3 operands
+(``_aim_block_forward_f8``).
 
 The window-attention branch (``wind_attn=True``, ``:212-287``, what the reference's two ``AIM`` recipes set together with
 ``not_shift=False``) is the second half of this file: per block, N = G G + 1 tokens per frame, d1 d2 the block's DropPath
@@ -43,8 +45,9 @@ from typing import Dict, List, Optional
 import torch
 
 from . import ops
-from .backbone import (BF16, F32, ViT_CLIP, _AdapterW, _embed_backward, _embed_forward, _empty, _Fork, _Frozen, _GradBufs,
-                       _ln_post_backward, _ln_post_forward, _mlp_adapter_backward, _mlp_adapter_forward, _wgrads_beside)
+from .backbone import (BF16, F32, ViT_CLIP, _AdapterW, _embed_backward, _embed_forward, _empty, _Fork, _Frozen, _Frozen8, _GradBufs,
+                       _ln_post_backward, _ln_post_forward, _mlp_adapter_backward, _mlp_adapter_forward,
+                       _mlp_adapter_forward_f8, _wgrads_beside)
 from .registry import BACKBONES
 from .win_block import (check_win_clip, check_window, clip_shift, clip_window, from_slot_layout, to_slot_layout, win_prompt_grad,
                         win_temporal_backward, win_temporal_forward)
@@ -128,9 +131,58 @@ def _spatial_backward(dx2b, c, fz: _Frozen, sad: _AdapterW, gS, later, BT, n, H,
     return dx1b, dqkv, delta, dxl
 
 
-def aim_block_forward(x, fz: _Frozen, adp: Dict[str, _AdapterW], B, T, N, H, dp1, dms2, save: bool):
+def _aim_block_forward_f8(x, fz: _Frozen, f8: _Frozen8, adp: Dict[str, _AdapterW], B, T, N, H, dp1, dms2):
+    """The stock block's forward on fp8 e4m3 operands (inference, M >= 1024): the QKV projection (twice), both out_proj GEMMs
+    and the MLP pair run ``aim_gemm_fp8``; their A operands are written as fp8 by the producing kernel -- ln_1 / ln_2, the
+    temporal attention (``tattn_fwd_infer``), the spatial attention, the [c_fc ; D_fc1] epilogue.  ``qkv``, ``ta`` and ``sa``
+    are bf16, T_Adapter and S_Adapter stay on the bf16 GEMMs, the residual stream stays fp32.  No context is kept."""
+    dev = x.device
+    M, D = x.shape
+    BT, r = B * T, fz.r
+    tad, sad = adp["T_Adapter"], adp["S_Adapter"]
+    # a forward without a backward has no reader for the adapters' pre-activations: the large-tile GEMM drops the stores of
+    # an absent `out2`; an adapter too narrow for that kernel writes into a scratch buffer
+    pre = None if (r >= 64 and r % 8 == 0) else _empty((M, r), BF16, dev)
+    # ---- temporal adaptation
+    xl = _empty((M, D), ops.FP8, dev)
+    ops.layernorm_fwd_fp8(x, fz.g1, fz.b1, M, D, D, xl)
+    qkv = _empty((M, 3 * D), BF16, dev)
+    ops.gemm_fp8(xl, f8.Wqkv, f8.sqkv, ops.EPI_BF16, qkv, bias=fz.bqkv)
+    ot = _empty((M, D), ops.FP8, dev)
+    ops.tattn_fwd_infer(qkv, ot, B, T, N, H)
+    ta = _empty((M, D), BF16, dev)
+    ops.gemm_fp8(ot, f8.Wo, f8.so, ops.EPI_BF16, ta, bias=fz.bo)
+    del ot
+    t_hs = _empty((M, r), BF16, dev)
+    ops.gemm(ta, tad.W1, ops.EPI_ACT, t_hs, bias=tad.b1, out2=pre, act=ops.ACT_GELU, at=dp1, ntok=N)
+    x1 = _empty((M, D), F32, dev)
+    ops.gemm(t_hs, tad.W2, ops.EPI_F32, x1, resid=x, vec=tad.b2.reshape(1, -1), ldv=0, bt=dp1, ntok=N)
+    del ta
+    # ---- spatial adaptation (the ln_1 and QKV buffers serve again)
+    ops.layernorm_fwd_fp8(x1, fz.g1, fz.b1, M, D, D, xl)
+    ops.gemm_fp8(xl, f8.Wqkv, f8.sqkv, ops.EPI_BF16, qkv, bias=fz.bqkv)
+    ao = _empty((M, D), ops.FP8, dev)
+    ops.attn_fwd_fp8(qkv, ao, BT, N, H)
+    sa = _empty((M, D), BF16, dev)
+    ops.gemm_fp8(ao, f8.Wo, f8.so, ops.EPI_BF16, sa, bias=fz.bo)
+    del ao, xl, qkv
+    ops.gemm(sa, sad.W1, ops.EPI_ACT, t_hs, bias=sad.b1, out2=pre, act=ops.ACT_GELU)
+    x2 = _empty((M, D), F32, dev)
+    ops.gemm(t_hs, sad.W2, ops.EPI_F32, x2, bias=sad.b2, resid=x1)      # x1 + D_fc2(GELU(D_fc1(sa)))
+    ops.acc_bf16(x2, sa)                                                # + sa: the adapter's skip connection
+    # ---- joint adaptation (shared with the vit_clip block)
+    return _mlp_adapter_forward_f8(x2, fz, f8, dms2, N)
+
+
+def aim_block_forward(x, fz: _Frozen, adp: Dict[str, _AdapterW], B, T, N, H, dp1, dms2, save: bool,
+                      f8: Optional[_Frozen8] = None, infer: bool = False):
     """x: [B*T*N, D] f32 frame-major -> x3.  ``dp1``: the first DropPath factor per token (no adapter scale,
-    vitclip_aim.py:205); ``dms2``: the second one times ``scale`` (:210)."""
+    vitclip_aim.py:205); ``dms2``: the second one times ``scale`` (:210).  ``infer`` (a no-grad forward; ``save`` must be
+    False): the temporal attention stores no probabilities -- same bits.  ``f8`` (with ``infer``): the block's fp8 operands,
+    and the large GEMMs run on them (``_aim_block_forward_f8``)."""
+    assert not (save and (infer or f8 is not None))
+    if f8 is not None:
+        return _aim_block_forward_f8(x, fz, f8, adp, B, T, N, H, dp1, dms2), None
     dev = x.device
     M, D = x.shape
     BT, r = B * T, fz.r
@@ -141,8 +193,12 @@ def aim_block_forward(x, fz: _Frozen, adp: Dict[str, _AdapterW], B, T, N, H, dp1
     qkv_t = _empty((M, 3 * D), BF16, dev)
     ops.gemm(xl, fz.Wqkv, ops.EPI_BF16, qkv_t, bias=fz.bqkv)
     ot = _empty((M, D), BF16, dev)
-    probs = _empty((B * N, H, T, T), F32, dev)
-    ops.tattn_fwd(qkv_t, ot, probs, B, T, N, H)
+    if infer:                           # no backward will read the probabilities: the form that does not store them
+        probs = None
+        ops.tattn_fwd_infer(qkv_t, ot, B, T, N, H)
+    else:
+        probs = _empty((B * N, H, T, T), F32, dev)
+        ops.tattn_fwd(qkv_t, ot, probs, B, T, N, H)
     ta = _empty((M, D), BF16, dev)
     ops.gemm(ot, fz.Wo, ops.EPI_BF16, ta, bias=fz.bo)
     del ot, xl

@@ -600,17 +600,7 @@ def _block_forward(x, fz: _Frozen, adp: Dict[str, _AdapterW], B, T, N, H, dms1, 
         epi_res, rdt = (ops.EPI_RES16, BF16) if r16 else (ops.EPI_F32, F32)
         x1 = _empty((M, D), rdt, dev)
         ops.gemm_fp8(ao, f8.Wo, f8.so, epi_res, x1, bias=fz.bo, resid=x, af=oml, vec=sv, bt=dms1, ntok=N)
-        xn = _empty((M, D), ops.FP8, dev)
-        if r16:
-            ops.layernorm_fwd_x16(x1, fz.g2, fz.b2, M, D, D, y8=xn)
-        else:
-            ops.layernorm_fwd_fp8(x1, fz.g2, fz.b2, M, D, D, xn)
-        hcat = _empty((M, H4 + r), ops.FP8, dev)
-        ops.gemm_fp8(xn, f8.Wcat1, f8.s1, ops.EPI_ACT8, hcat, bias=fz.bcat1, act=ops.ACT_QGELU, n_split=H4,
-                     act2=ops.ACT_GELU, at=dms2, ntok=N)
-        x2 = _empty((M, D), rdt, dev)
-        ops.gemm_fp8(hcat, f8.Wcat2, f8.s2, epi_res, x2, bias=fz.bpr, resid=x1, vec=fz.b2row, ldv=0, bt=dms2, ntok=N)
-        return x2, None
+        return _mlp_adapter_forward_f8(x1, fz, f8, dms2, N), None
     if top:
         # the class rows as the only token: resid = rows n == 0 of x (row stride N * D), factors of token 0.  small_tile: the
         # 64 x 64 kernel sums K in the 256 x 256 kernel's order, so these rows get the bits the full-row launch gave them
@@ -668,6 +658,28 @@ def _mlp_adapter_forward(x1, fz: _Frozen, dms2, N, save: bool, small_tile: bool 
     # price of keeping hcat (M x (4D + r) bf16) alive until this block's backward
     a_s = hcat[:, H4:] if save else None
     return x2, xn, mean2, rstd2, hcat_pre, a_s
+
+
+def _mlp_adapter_forward_f8(x1, fz: _Frozen, f8: _Frozen8, dms2, N):
+    """The joint adaptation of ``_mlp_adapter_forward`` on fp8 operands (inference): ln_2 writes fp8, [c_fc ; D_fc1] writes its
+    activations as fp8 (``EPI_ACT8``), [c_proj | D_fc2] adds to the residual stream in the stream's own type -- bf16
+    (``EPI_RES16``) or fp32.  Shared by the ViT_CLIP block and the stock-AIM block (aim_variant.py).  Returns x2."""
+    dev = x1.device
+    M, D = x1.shape
+    r, H4 = fz.r, 4 * D
+    r16 = x1.dtype == BF16
+    epi_res, rdt = (ops.EPI_RES16, BF16) if r16 else (ops.EPI_F32, F32)
+    xn = _empty((M, D), ops.FP8, dev)
+    if r16:
+        ops.layernorm_fwd_x16(x1, fz.g2, fz.b2, M, D, D, y8=xn)
+    else:
+        ops.layernorm_fwd_fp8(x1, fz.g2, fz.b2, M, D, D, xn)
+    hcat = _empty((M, H4 + r), ops.FP8, dev)
+    ops.gemm_fp8(xn, f8.Wcat1, f8.s1, ops.EPI_ACT8, hcat, bias=fz.bcat1, act=ops.ACT_QGELU, n_split=H4,
+                 act2=ops.ACT_GELU, at=dms2, ntok=N)
+    x2 = _empty((M, D), rdt, dev)
+    ops.gemm_fp8(hcat, f8.Wcat2, f8.s2, epi_res, x2, bias=fz.bpr, resid=x1, vec=fz.b2row, ldv=0, bt=dms2, ntok=N)
+    return x2
 
 
 def _mlp_adapter_backward(dyb, x_in, mean2, rstd2, xn, hcat_pre, a_s, dms2, fz: _Frozen, gm, N, fsum=None,
@@ -1010,12 +1022,12 @@ class _BackboneFn(torch.autograd.Function):
         training = model.training
         f8 = None
         if model.inference_precision == 'fp8' and not need_grad:
-            if M >= 1024 and model.variant == 'vit_clip':
+            if M >= 1024 and model.variant in ('vit_clip', 'aim'):
                 f8 = model._fp8_operands()
             elif not getattr(model, "_fp8_warned", False):
                 model._fp8_warned = True
                 _LOG.warning("fp8 inference was requested but this forward runs bf16: %s",
-                             "the stock-AIM variant has no fp8 path" if model.variant != 'vit_clip'
+                             "this variant has no fp8 path" if model.variant not in ('vit_clip', 'aim')
                              else "fewer than 1024 token rows (M = %d)" % M)
         masks = model._drop_masks(N, training, dev)          # [L, 2, N]: all layers' DropPath factors in three launches
         aim = model.variant == 'aim'
@@ -1033,11 +1045,12 @@ class _BackboneFn(torch.autograd.Function):
             dms1, dms2 = masks[i, 0], masks[i, 1]
             if aim:      # stock-AIM block: its first DropPath acts on the un-scaled temporal branch (vitclip_aim.py:205)
                 scale = float(model.transformer.resblocks[i].scale)
-                return aim_block_forward(x_in, frozen["blocks"][i], adp[i], B, T, N, H, dms1 * (1.0 / scale), dms2, save)
+                return aim_block_forward(x_in, frozen["blocks"][i], adp[i], B, T, N, H, dms1 * (1.0 / scale), dms2, save,
+                                         f8=None if f8 is None else f8[i], infer=not need_grad)
             return _block_forward(x_in, frozen["blocks"][i], adp[i], B, T, N, H, dms1, dms2, save,
                                   f8=None if f8 is None else f8[i], top=top and i == L - 1)
 
-        if f8 is not None and _FP8_RES16:            # the fp8 path's residual stream is bf16
+        if f8 is not None and _FP8_RES16 and not aim:     # ViT_CLIP's fp8 path keeps its residual stream in bf16 (stock AIM's: fp32)
             x16 = _empty((M, D), BF16, dev)
             ops.cast_bf16(x, x16)
             x = x16

@@ -14,11 +14,24 @@ namespace {
 
 constexpr int TMAX = 32;
 
-// LDS per wave: q, k, v [T][65] f32 + p [T][T+1]
-__device__ __forceinline__ int tattn_lds_floats(int T) { return 3 * T * 65 + T * (T + 1); }
+// How q, k and v are staged in LDS: as fp32 in rows of 65 floats, or (LDS16) as the bf16 they arrive as in rows of 66
+// elements (33 dwords: an odd dword stride again) and widened on read -- the same fp32 values, half the bytes.
+template <bool LDS16> struct tattn_stage { typedef float elem; static constexpr int RS = 65, ROW_FLOATS = 65; };
+template <> struct tattn_stage<true> { typedef bf16_t elem; static constexpr int RS = 66, ROW_FLOATS = 33; };
 
-__global__ __launch_bounds__(256) void tattn_fwd_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
+// LDS per wave: q, k, v [T][RS] + p [T][T+1] f32
+template <bool LDS16>
+__host__ __device__ __forceinline__ int tattn_lds_floats(int T) { return 3 * T * tattn_stage<LDS16>::ROW_FLOATS + T * (T + 1); }
+
+// PROBS: the probabilities go to `probs` (what the backward reads).  OUT8: `out` is e4m3 bytes, the saturating cast of the
+// fp32 accumulators, instead of bf16.  <true, false, false> is the training forward; the others are the inference forms
+// (aim_tattn_fwd_infer).  The score, softmax and P.V arithmetic is one text for all of them, every sum in ascending index
+// order, so the bf16 outputs agree bit for bit and the fp8 bytes are the cast of the very accumulators the bf16 form rounds.
+template <bool PROBS, bool OUT8, bool LDS16>
+__global__ __launch_bounds__(256) void tattn_fwd_kernel(const bf16_t* __restrict__ qkv, void* __restrict__ out,
                                                         float* __restrict__ probs, int B, int T, int N, int H) {
+    typedef typename tattn_stage<LDS16>::elem S;
+    constexpr int RS = tattn_stage<LDS16>::RS;
     extern __shared__ float smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long long prob = (long long)blockIdx.x * (blockDim.x >> 6) + wave;          // (b, n, h)
@@ -28,23 +41,34 @@ __global__ __launch_bounds__(256) void tattn_fwd_kernel(const bf16_t* __restrict
     const long long bn = prob / H;
     const int n = (int)(bn % N), b = (int)(bn / N);
     const int D = H * 64, ld = 3 * D;
-    float* sq = smem + wave * tattn_lds_floats(T);
-    float* sk = sq + T * 65;
-    float* sv = sk + T * 65;
-    float* sp = sv + T * 65;
+    S* sq = (S*)(smem + wave * tattn_lds_floats<LDS16>(T));
+    S* sk = sq + T * RS;
+    S* sv = sk + T * RS;
+    float* sp = (float*)(sv + T * RS);
     for (int t = 0; t < T; ++t) {
         const bf16_t* r = qkv + ((long long)(b * T + t) * N + n) * ld + h * 64 + lane;
-        sq[t * 65 + lane] = (float)r[0];
-        sk[t * 65 + lane] = (float)r[D];
-        sv[t * 65 + lane] = (float)r[2 * D];
+        sq[t * RS + lane] = (S)r[0];
+        sk[t * RS + lane] = (S)r[D];
+        sv[t * RS + lane] = (S)r[2 * D];
     }
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_s_waitcnt(0xC07F);          // lgkmcnt(0): this wave's LDS writes are done
     for (int p = lane; p < T * T; p += 64) {
         const int tq = p / T, tk = p - tq * T;
         float acc = 0.f;
+        if constexpr (LDS16) {      // two elements per 32-bit LDS read, summed in the same ascending order
+            const bf16x2* q2 = (const bf16x2*)(sq + tq * RS);
+            const bf16x2* k2 = (const bf16x2*)(sk + tk * RS);
 #pragma unroll 8
-        for (int d = 0; d < 64; ++d) acc += sq[tq * 65 + d] * sk[tk * 65 + d];
+            for (int d = 0; d < 32; ++d) {
+                const bf16x2 a = q2[d], c = k2[d];
+                acc += (float)a[0] * (float)c[0];
+                acc += (float)a[1] * (float)c[1];
+            }
+        } else {
+#pragma unroll 8
+            for (int d = 0; d < 64; ++d) acc += sq[tq * RS + d] * sk[tk * RS + d];
+        }
         sp[tq * (T + 1) + tk] = acc * 0.125f;
     }
     __builtin_amdgcn_wave_barrier();
@@ -62,15 +86,42 @@ __global__ __launch_bounds__(256) void tattn_fwd_kernel(const bf16_t* __restrict
         for (int tk = 0; tk < T; ++tk) {
             const float p = sp[tq * (T + 1) + tk] * inv;
             sp[tq * (T + 1) + tk] = p;
-            probs[(prob * T + tq) * T + tk] = p;
+            if constexpr (PROBS) probs[(prob * T + tq) * T + tk] = p;
         }
     }
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_s_waitcnt(0xC07F);
-    for (int tq = 0; tq < T; ++tq) {
-        float acc = 0.f;
-        for (int tk = 0; tk < T; ++tk) acc += sp[tq * (T + 1) + tk] * sv[tk * 65 + lane];
-        out[((long long)(b * T + tq) * N + n) * D + h * 64 + lane] = (bf16_t)acc;
+    if constexpr (OUT8) {
+        // a lane owns four consecutive head-dim elements (one packed 32-bit store) of query row tq0 + lane / 16: sixteen
+        // lanes cover the head's 64 bytes of a row, the wave four rows per step
+        const int sub = lane >> 4, d4 = (lane & 15) * 4;
+        for (int tq0 = 0; tq0 < T; tq0 += 4) {
+            const int tq = tq0 + sub;
+            if (tq >= T) continue;
+            float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+            for (int tk = 0; tk < T; ++tk) {
+                const float p = sp[tq * (T + 1) + tk];
+                float v0, v1, v2, v3;
+                if constexpr (LDS16) {
+                    const bf16x2* v = (const bf16x2*)(sv + tk * RS + d4);
+                    const bf16x2 lo = v[0], hi = v[1];
+                    v0 = (float)lo[0], v1 = (float)lo[1], v2 = (float)hi[0], v3 = (float)hi[1];
+                } else {
+                    v0 = sv[tk * RS + d4], v1 = sv[tk * RS + d4 + 1], v2 = sv[tk * RS + d4 + 2], v3 = sv[tk * RS + d4 + 3];
+                }
+                a0 += p * v0;
+                a1 += p * v1;
+                a2 += p * v2;
+                a3 += p * v3;
+            }
+            *(unsigned*)((uint8_t*)out + ((long long)(b * T + tq) * N + n) * D + h * 64 + d4) = pack4_fp8(a0, a1, a2, a3);
+        }
+    } else {
+        for (int tq = 0; tq < T; ++tq) {
+            float acc = 0.f;
+            for (int tk = 0; tk < T; ++tk) acc += sp[tq * (T + 1) + tk] * (float)sv[tk * RS + lane];
+            ((bf16_t*)out)[((long long)(b * T + tq) * N + n) * D + h * 64 + lane] = (bf16_t)acc;
+        }
     }
 }
 
@@ -167,21 +218,43 @@ __global__ __launch_bounds__(256) void acc_bf16_kernel(float* __restrict__ x, co
 
 }  // namespace
 
+template <bool PROBS, bool OUT8, bool LDS16>
+static int tattn_fwd_launch(const char* name, const aim_bf16* qkv, void* out, float* probs, int B, int T, int N, int H, void* stream) {
+    const long long nprob = (long long)B * N * H;
+    const int wpb = T <= 16 ? 4 : 2;                // waves (problems) per workgroup: LDS per problem grows with T
+    const size_t lds = (size_t)wpb * tattn_lds_floats<LDS16>(T) * 4;
+    static bool attr_set_f = false;                 // (one per instantiation)
+    if (!attr_set_f) {
+        (void)hipFuncSetAttribute((const void*)tattn_fwd_kernel<PROBS, OUT8, LDS16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        attr_set_f = true;
+    }
+    hipLaunchKernelGGL((tattn_fwd_kernel<PROBS, OUT8, LDS16>), dim3((unsigned)((nprob + wpb - 1) / wpb)), dim3(64 * wpb), lds,
+                       (hipStream_t)stream, (const bf16_t*)qkv, out, probs, B, T, N, H);
+    AIM_CHECK_LAUNCH(name);
+    return 0;
+}
+
 extern "C" int aim_tattn_fwd(const aim_bf16* qkv, aim_bf16* out, float* probs, int B, int T, int N, int H, void* stream) {
     AIM_CHECK_ARG(B > 0 && T > 0 && T <= TMAX && N > 0 && H > 0, "tattn_fwd: unsupported shape B=%d T=%d (T <= 32)", B, T);
     AIM_CHECK_ARG(qkv && out && probs, "tattn_fwd: null pointer");
-    const long long nprob = (long long)B * N * H;
-    const int wpb = T <= 16 ? 4 : 2;                // waves (problems) per workgroup: LDS per problem grows with T
-    const size_t lds = (size_t)wpb * (3 * T * 65 + T * (T + 1)) * 4;
-    static bool attr_set_f = false;
-    if (!attr_set_f) {
-        (void)hipFuncSetAttribute((const void*)tattn_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set_f = true;
+    return tattn_fwd_launch<true, false, false>("aim_tattn_fwd", qkv, out, probs, B, T, N, H, stream);
+}
+
+extern "C" int aim_tattn_fwd_infer(const aim_bf16* qkv, aim_bf16* out, uint8_t* out_fp8, int B, int T, int N, int H, void* stream) {
+    AIM_CHECK_ARG(B > 0 && T > 0 && T <= TMAX && N > 0 && H > 0, "tattn_fwd_infer: unsupported shape B=%d T=%d (T <= 32)", B, T);
+    AIM_CHECK_ARG(qkv, "tattn_fwd_infer: null pointer");
+    AIM_CHECK_ARG((out != nullptr) != (out_fp8 != nullptr), "tattn_fwd_infer: exactly one of out / out_fp8 must be given");
+    AIM_CHECK_ARG(((uintptr_t)out_fp8 & 3) == 0, "tattn_fwd_infer: out_fp8 must be 4-byte aligned (packed 32-bit stores)");
+    // q, k, v staged as bf16: 16.5 KB instead of 28.5 KB per wave at T = 32, so twice the waves fit a CU and a score or P.V
+    // step reads two elements per LDS access.  Measured at 3 views x 32 frames x 257 tokens x 16 heads (rocprofv3): bf16
+    // form 415 -> 264 us, fp8 form 362 -> 209 us, same bits.  AIM_TATTN_LDS16=0: fp32 staging as in the training kernel (A/B runs)
+    static const bool lds16 = [] { const char* e = getenv("AIM_TATTN_LDS16"); return !e || atoi(e) != 0; }();
+    if (out_fp8) {
+        if (lds16) return tattn_fwd_launch<false, true, true>("aim_tattn_fwd_infer", qkv, out_fp8, nullptr, B, T, N, H, stream);
+        return tattn_fwd_launch<false, true, false>("aim_tattn_fwd_infer", qkv, out_fp8, nullptr, B, T, N, H, stream);
     }
-    hipLaunchKernelGGL(tattn_fwd_kernel, dim3((unsigned)((nprob + wpb - 1) / wpb)), dim3(64 * wpb), lds, (hipStream_t)stream, (const bf16_t*)qkv,
-                       (bf16_t*)out, probs, B, T, N, H);
-    AIM_CHECK_LAUNCH("aim_tattn_fwd");
-    return 0;
+    if (lds16) return tattn_fwd_launch<false, false, true>("aim_tattn_fwd_infer", qkv, out, nullptr, B, T, N, H, stream);
+    return tattn_fwd_launch<false, false, false>("aim_tattn_fwd_infer", qkv, out, nullptr, B, T, N, H, stream);
 }
 
 extern "C" int aim_tattn_bwd(const aim_bf16* qkv, const float* probs, const aim_bf16* dout, aim_bf16* dqkv, int B, int T, int N,

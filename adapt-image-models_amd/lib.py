@@ -84,6 +84,7 @@ SIGNATURES = {
     "aim_cls_attn_fwd": [P, P, P, I, I, I, I, P],
     "aim_cls_attn_bwd": [P, P, P, P, I, I, I, I, I, P],
     "aim_tattn_fwd": [P, P, P, I, I, I, I, P],
+    "aim_tattn_fwd_infer": [P, P, P, I, I, I, I, P],
     "aim_tattn_bwd": [P, P, P, P, I, I, I, I, P],
     "aim_add_bf16": [P, L, P, L, P, L, I, I, P],
     "aim_acc_bf16": [P, P, L, I, I, P],
@@ -128,7 +129,7 @@ SIGNATURES = {
     "aim_layernorm_gb_bwd": [P, I, L, P, L, P, P, P, P, I, I, P, L, P],
 }
 
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 
 def load_library():

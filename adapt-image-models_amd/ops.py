@@ -527,6 +527,21 @@ def tattn_fwd(qkv, out, probs, B, T, N, H):
     check(load_library().aim_tattn_fwd(qkv.data_ptr(), out.data_ptr(), probs.data_ptr(), B, T, N, H, _stream()), "aim_tattn_fwd")
 
 
+def tattn_fwd_infer(qkv, out, B, T, N, H):
+    """``tattn_fwd`` for a forward without a backward: no probabilities are stored.  ``out`` [M, D] bf16 gets the bits
+    ``tattn_fwd`` writes; a 1-byte dtype (fp8 e4m3 / uint8) gets the saturating e4m3 cast of the same fp32 accumulators."""
+    _chk(qkv, BF16, "qkv")
+    if not out.is_cuda or not out.is_contiguous():
+        raise TypeError("out: expected a contiguous GPU tensor")
+    if out.dtype == BF16:
+        o16, o8 = out.data_ptr(), None
+    elif out.element_size() == 1:
+        o16, o8 = None, out.data_ptr()
+    else:
+        raise TypeError(f"out: expected bf16 or a 1-byte (fp8) dtype, got {out.dtype}")
+    check(load_library().aim_tattn_fwd_infer(qkv.data_ptr(), o16, o8, B, T, N, H, _stream()), "aim_tattn_fwd_infer")
+
+
 def tattn_bwd(qkv, probs, dout, dqkv, B, T, N, H):
     _chk(qkv, BF16, "qkv"); _chk(probs, F32, "probs"); _chk(dout, BF16, "dout"); _chk(dqkv, BF16, "dqkv")
     check(load_library().aim_tattn_bwd(qkv.data_ptr(), probs.data_ptr(), dout.data_ptr(), dqkv.data_ptr(), B, T, N, H, _stream()),

@@ -32,7 +32,7 @@ extern "C" {
 
 typedef uint16_t aim_bf16;
 
-#define AIM_ABI_VERSION 14
+#define AIM_ABI_VERSION 15
 
 int aim_version(void);                /* == AIM_ABI_VERSION */
 const char* aim_last_error(void);     /* message of the last failing call on this thread */
@@ -347,6 +347,13 @@ int aim_cls_attn_bwd(const aim_bf16* qkv, const float* probs, const aim_bf16* do
 int aim_tattn_fwd(const aim_bf16* qkv, aim_bf16* out, float* probs, int B, int T, int N, int H, void* stream);
 int aim_tattn_bwd(const aim_bf16* qkv, const float* probs, const aim_bf16* dout, aim_bf16* dqkv, int B, int T, int N, int H,
                   void* stream);
+/* inference forms of aim_tattn_fwd (ABI 15): no probabilities are stored (a forward without a backward has no reader for
+ * them: at T = 32 they are 4 KB of stores per (token, head) beside 12 KB of loads).  Exactly one of out / out_fp8 is
+ * non-NULL; both or neither is refused before any launch.  Same shapes as aim_tattn_fwd (T <= 32).
+ *   out     [B*T*N, D] bf16 : the bits aim_tattn_fwd writes to `out`
+ *   out_fp8 [B*T*N, D] e4m3 : the saturating cast (|x| clamped to 448) of the same fp32 accumulators -- the A operand of
+ *                             the fp8 out_proj GEMM (aim_gemm_fp8); written as packed 32-bit stores, 4-byte aligned */
+int aim_tattn_fwd_infer(const aim_bf16* qkv, aim_bf16* out, uint8_t* out_fp8, int B, int T, int N, int H, void* stream);
 int aim_add_bf16(const aim_bf16* a, int64_t lda, const aim_bf16* b, int64_t ldb, aim_bf16* out, int64_t ldo, int R, int C,
                  void* stream);
 int aim_acc_bf16(float* x, const aim_bf16* s, int64_t lds, int R, int C, void* stream);
