@@ -236,17 +236,8 @@ def aim_block_backward(dyb, c, fz: _Frozen, adp: Dict[str, _AdapterW], grads, B,
     dxb = _empty((M, D), BF16, dev)
     ops.layernorm_bwd(dxl, c["x"], fz.g1, c["mean1"], c["rstd1"], M, D, lddy=D, ldx=D, lddx=D, dres=dx1b, dx_bf16=dxb)
     # the six weight gradients + bias column sums: off the gradient path, on the detached stream behind the main stream's
-    # work so far
-    fork = _Fork(dev, "aim-bwd")
-    if fork.enabled:
-        fork.started = True
-        fork.sync_side_to_main()
-    standalone = keep is None
-    if standalone:
-        keep = []
-    fork.run_detached(later, keep)
-    if standalone:
-        _Fork.join_detached(dev)
+    # work so far (``keep`` None, stand-alone use: inline, complete when this function returns)
+    _wgrads_beside(_Fork(dev, "aim-bwd"), later, keep)
     return dxb
 
 

@@ -11,6 +11,7 @@ forward AND backward (frozen GEMMs need dgrad only) -- see DESIGN.md.
 There is no eager/CPU fallback: ``forward`` raises unless the input is on a GPU and the HIP
 library is built.
 """
+import contextlib
 import logging
 import os
 from collections import OrderedDict
@@ -242,15 +243,11 @@ def join_stats():
         _JOIN_STATS.clear()
     return out
 _USE_SIDE = os.environ.get("AIM_SIDE_STREAM", "1") != "0"
-_LAMBDA_ON_SIDE = os.environ.get("AIM_LAMBDA_SIDE", "1") != "0"
-_LATE_JOIN = os.environ.get("AIM_LATE_JOIN", "1") != "0"
-_FSUM_IN_LN = os.environ.get("AIM_FSUM_IN_LN", "1") != "0"     # (A/B switch) per-frame d(x1) sums from the ln_2 backward
-_CLS_EARLY = os.environ.get("AIM_CLS_EARLY", "1") != "0"
-_LAMBDA_FUSED = os.environ.get("AIM_LAMBDA_FUSED", "1") != "0"
 _DETACH_WGRAD = os.environ.get("AIM_DETACH_WGRAD", "1") != "0"
 _DETACH_BIG = os.environ.get("AIM_DETACH_BIG", "1") != "0"
-_EXPSUM_DETACHED = os.environ.get("AIM_EXPSUM_DETACHED", "0") != "0"      # measured: -0.7 % (the GEMM doubles beside the attention)
-_DETACHED_PRIORITY = int(os.environ.get("AIM_DETACHED_PRIORITY", "0"))   # HIP stream priority of the weight-gradient stream
+# HIP stream priorities.  High for the side stream: it carries a dozen tiny kernels that the main stream later waits for
+_SIDE_STREAM_PRIORITY = -1
+_WGRAD_STREAM_PRIORITY = 0          # the detached (weight-gradient) stream
 # The buffers the activations' backward reads (`hcat_pre`, the adapters' `pre`) hold the activation's DERIVATIVE at the
 # pre-activation, written by the forward epilogue, instead of the pre-activation itself (aim_gemm_args.aux_grad): the dgrad
 # epilogues lose their exp / rcp.  AIM_AUX_GRAD=0 restores the pre-activation form (A/B runs).
@@ -263,12 +260,11 @@ _AUX_FRAG = os.environ.get("AIM_AUX_FRAG", "1") != "0" and os.environ.get("AIM_G
 # every N = 768 GEMM a whole tile round (1 182 tiles: 5 rounds on 256 CUs, 6 on 224: +20 %).  Unmeasured on > 1 GPU.
 _DP_RESERVE = int(os.environ.get("AIM_DP_RESERVE_CUS", "0"))
 _FP8_RES16 = os.environ.get("AIM_FP8_RES16", "1") != "0"      # fp8 inference: bf16 residual stream (0: fp32, the A/B form)
-_EXPSUM_BORDER = os.environ.get("AIM_EXPSUM_BORDER", "1") != "0"      # N = 257: one 256 x 256 tile per frame + aim_qk_border
 # The head reads the class row of every frame and nothing else (ln_post, _BackboneFn.forward), so the LAST block computes its
 # spatial attention output, out_proj, ln_2 and the MLP + MLP_Adapter for those B*T rows only, and its backward starts from a
 # compact [B*T, D] gradient.  0 = the full-row last block (A/B runs and the equivalence test).
 _TOP_CLS_ONLY = os.environ.get("AIM_TOP_CLS_ONLY", "1") != "0"
-_QKV_RESERVE = int(os.environ.get("AIM_QKV_RESERVE", "32"))     # CUs the forward QKV GEMM leaves to the class-token chain (measured: 0/8/16 equal, 32 +0.7 %, 48 equal)
+_QKV_RESERVE = 32     # CUs the forward QKV GEMM leaves to the class-token chain (measured: 0/8/16 equal, 32 +0.7 %, 48 equal)
 
 
 class _Fork:
@@ -286,24 +282,35 @@ class _Fork:
         if self.enabled:
             key = (dev.type, dev.index)
             if key not in _SIDE:
-                # high priority: the side stream carries a dozen tiny kernels that the main stream later waits for
-                _SIDE[key] = torch.cuda.Stream(device=dev, priority=int(os.environ.get("AIM_SIDE_PRIORITY", "-1")))
+                _SIDE[key] = torch.cuda.Stream(device=dev, priority=_SIDE_STREAM_PRIORITY)
             self.side_stream = _SIDE[key]
             self.main = torch.cuda.current_stream(dev)
+
+    @staticmethod
+    def _wait(stream, ev, tag: str):
+        """``stream`` waits for ``ev``; with AIM_JOIN_STATS=1 the time it sits in that wait is recorded under ``tag``."""
+        if _JOIN_STATS is None:
+            stream.wait_event(ev)
+            return
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        stream.wait_event(ev)
+        e1.record(stream)
+        _JOIN_STATS.append((tag, e0, e1))
+
+    def _detached_stream(self):
+        """The device's third stream (weight gradients), created on first use."""
+        key = (self.dev.type, self.dev.index)
+        if key not in _DETACHED:
+            _DETACHED[key] = torch.cuda.Stream(device=self.dev, priority=_WGRAD_STREAM_PRIORITY)
+        return _DETACHED[key]
 
     def sync_main_to_side(self):
         """The main stream waits for everything queued on the side stream so far."""
         if self.enabled and self.started:
             ev = torch.cuda.Event()
             ev.record(self.side_stream)
-            if _JOIN_STATS is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(self.main)
-                self.main.wait_event(ev)
-                e1.record(self.main)
-                _JOIN_STATS.append((self.tag + "-mid", e0, e1))
-                return
-            self.main.wait_event(ev)
+            self._wait(self.main, ev, self.tag + "-mid")
 
     def sync_side_to_main(self):
         """The side stream waits for everything queued on the main stream so far."""
@@ -312,32 +319,23 @@ class _Fork:
             ev.record(self.main)
             self.side_stream.wait_event(ev)
 
+    @contextlib.contextmanager
     def side(self):
-        fork = self
-
-        class _Section:
-            def __enter__(self_inner):
-                if fork.enabled:
-                    if not fork.started:
-                        fork.started = True
-                        fork.sync_side_to_main()
-                    self_inner.ctx = torch.cuda.stream(fork.side_stream)
-                    self_inner.ctx.__enter__()
-                    if _JOIN_STATS is not None:      # diagnostics: the section's own span on the side stream
-                        self_inner.t0 = torch.cuda.Event(enable_timing=True)
-                        self_inner.t0.record(fork.side_stream)
-                return fork
-
-            def __exit__(self_inner, *exc):
-                if fork.enabled:
-                    if _JOIN_STATS is not None:
-                        t1 = torch.cuda.Event(enable_timing=True)
-                        t1.record(fork.side_stream)
-                        _JOIN_STATS.append((fork.tag + "-span", self_inner.t0, t1))
-                    self_inner.ctx.__exit__(*exc)
-                return False
-
-        return _Section()
+        """One side section (a no-op context when the streams are off)."""
+        if not self.enabled:
+            yield self
+            return
+        if not self.started:
+            self.started = True
+            self.sync_side_to_main()
+        with torch.cuda.stream(self.side_stream):
+            if _JOIN_STATS is not None:      # diagnostics: the section's own span on the side stream
+                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                t0.record(self.side_stream)
+            yield self
+            if _JOIN_STATS is not None:
+                t1.record(self.side_stream)
+                _JOIN_STATS.append((self.tag + "-span", t0, t1))
 
     # ``with _Fork(dev) as f:`` = one side section
     def __enter__(self):
@@ -350,23 +348,15 @@ class _Fork:
     def run_detached(self, calls: list, keep: list):
         """Run ``calls`` (closures launching kernels) after the side stream's work so far, on a third stream that nothing
         waits for until ``join_detached``.  ``keep`` receives the closures so that the tensors they captured (allocated
-        on other streams) outlive their use."""
+        on other streams) outlive their use.  Without the detached stream they run as one more side section."""
         if not calls:
             return
         if not (self.enabled and _DETACH_WGRAD):
-            ctx = self.side() if self.enabled else None
-            if ctx is not None:
-                with ctx:
-                    for f in calls:
-                        f()
-            else:
+            with self.side():
                 for f in calls:
                     f()
             return
-        key = (self.dev.type, self.dev.index)
-        if key not in _DETACHED:
-            _DETACHED[key] = torch.cuda.Stream(device=self.dev, priority=_DETACHED_PRIORITY)
-        w = _DETACHED[key]
+        w = self._detached_stream()
         ev = torch.cuda.Event()
         ev.record(self.side_stream)
         w.wait_event(ev)
@@ -376,23 +366,16 @@ class _Fork:
         keep.extend(calls)
 
     def run_beside(self, fn):
-        """Run ``fn`` on the third stream, ordered after the main stream's work so far; returns the event that marks
-        its completion (None when streams are off: ``fn`` then ran inline)."""
+        """Run ``fn`` on the third stream, ordered after the main stream's work so far (inline when streams are off)."""
         if not self.enabled:
             fn()
-            return None
-        key = (self.dev.type, self.dev.index)
-        if key not in _DETACHED:
-            _DETACHED[key] = torch.cuda.Stream(device=self.dev, priority=_DETACHED_PRIORITY)
-        w = _DETACHED[key]
+            return
+        w = self._detached_stream()
         ev = torch.cuda.Event()
         ev.record(self.main)
         w.wait_event(ev)
         with torch.cuda.stream(w):
             fn()
-        done = torch.cuda.Event()
-        done.record(w)
-        return done
 
     @staticmethod
     def streams(dev):
@@ -411,28 +394,13 @@ class _Fork:
         if w is not None:
             ev = torch.cuda.Event()
             ev.record(w)
-            main = torch.cuda.current_stream(dev)
-            if _JOIN_STATS is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(main)
-                main.wait_event(ev)
-                e1.record(main)
-                _JOIN_STATS.append(("detached", e0, e1))
-                return
-            main.wait_event(ev)
+            _Fork._wait(torch.cuda.current_stream(dev), ev, "detached")
 
     def join(self):
         if self.enabled and self.started:
             done = torch.cuda.Event()
             done.record(self.side_stream)
-            if _JOIN_STATS is not None:      # diagnostics: how long the main stream sits in this wait
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(self.main)
-                self.main.wait_event(done)
-                e1.record(self.main)
-                _JOIN_STATS.append((self.tag, e0, e1))
-                return
-            self.main.wait_event(done)
+            self._wait(self.main, done, self.tag)      # (diagnostics: how long the main stream sits in this wait)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -467,15 +435,22 @@ def _block_forward(x, fz: _Frozen, adp: Dict[str, _AdapterW], B, T, N, H, dms1, 
     r = fz.r
     # Class-token path on the side stream: temporal attention over the class tokens + T_Adapter (vit_clip.py:220-229),
     # then the cross term.  It needs q/k/v of the B*T class rows only, so those are projected apart (ln_1 + QKV on
-    # 512 rows) and the chain starts beside the big ln_1 / QKV GEMM instead of after them (AIM_CLS_EARLY=0: after).
+    # 512 rows) and the chain starts beside the big ln_1 / QKV GEMM instead of after them.
     fork = _Fork(dev, "fwd")
     # every tensor a side-stream kernel writes comes out of this main-stream buffer (see _Arena)
     ar = _Arena(dev, 48 * BT * D + 4 * B * H * T * T + 8 * BT * N + (1 << 16))
-
-    def cls_chain(qkv_src, n_stride):
+    with fork.side():
+        xl_cls = ar.take((BT, D), BF16)
+        if x.dtype == BF16:      # (the fp8 path's residual stream is bf16)
+            ops.layernorm_fwd_x16(x, fz.g1, fz.b1, BT, D, N * D, y_bf16=xl_cls)
+        else:
+            ops.layernorm_fwd(x, fz.g1, fz.b1, BT, D, N * D, y_bf16=xl_cls, mean=ar.take((BT,), F32),
+                              rstd=ar.take((BT,), F32))
+        qkv_cls = ar.take((BT, 3 * D), BF16)
+        ops.gemm(xl_cls, fz.Wqkv, ops.EPI_BF16, qkv_cls, bias=fz.bqkv)
         ot = ar.take((BT, D), BF16)
         probs = ar.take((B, H, T, T), F32)
-        ops.cls_attn_fwd(qkv_src, ot, probs, B, T, n_stride, H)
+        ops.cls_attn_fwd(qkv_cls, ot, probs, B, T, 1, H)      # "N = 1": the rows ARE the class tokens
         ta = ar.take((BT, D), BF16)
         ops.gemm(ot, fz.Wo, ops.EPI_BF16, ta, bias=fz.bo)
         xt, t_pre, t_h = _adapter_fwd_small(ta, adp["T_Adapter"], BT, r, D, ar, out_f32=False)
@@ -484,22 +459,9 @@ def _block_forward(x, fz: _Frozen, adp: Dict[str, _AdapterW], B, T, N, H, dms1, 
         ops.gemm(xt, fz.Wqkv[D:], ops.EPI_BF16, kv, bias=fz.bqkv[D:])
         crs = ar.take((BT, D), F32)
         ops.gemm(kv[:, D:], fz.Wo, ops.EPI_F32, crs, bias=fz.bo)
-        return probs, ta, t_pre, t_h, kv, crs
-
-    if _CLS_EARLY:
-        with fork.side():
-            xl_cls = ar.take((BT, D), BF16)
-            if x.dtype == BF16:      # (the fp8 path's residual stream is bf16)
-                ops.layernorm_fwd_x16(x, fz.g1, fz.b1, BT, D, N * D, y_bf16=xl_cls)
-            else:
-                ops.layernorm_fwd(x, fz.g1, fz.b1, BT, D, N * D, y_bf16=xl_cls, mean=ar.take((BT,), F32),
-                                  rstd=ar.take((BT,), F32))
-            qkv_cls = ar.take((BT, 3 * D), BF16)
-            ops.gemm(xl_cls, fz.Wqkv, ops.EPI_BF16, qkv_cls, bias=fz.bqkv)
-            probs, ta, t_pre, t_h, kv, crs = cls_chain(qkv_cls, 1)      # "N = 1": the rows ARE the class tokens
     # main stream: ln_1 (once) + fused QKV projection
     qkv = _empty((M, 3 * D), BF16, dev)
-    reserve = _QKV_RESERVE if (_CLS_EARLY and fork.enabled) else 0     # CUs left to the class-token chain (per-call argument)
+    reserve = _QKV_RESERVE if fork.enabled else 0     # CUs left to the class-token chain (per-call argument)
     if f8 is not None:
         xl = _empty((M, D), ops.FP8, dev)
         mean1 = rstd1 = None
@@ -514,14 +476,10 @@ def _block_forward(x, fz: _Frozen, adp: Dict[str, _AdapterW], B, T, N, H, dms1, 
         ops.layernorm_fwd(x, fz.g1, fz.b1, M, D, D, y_bf16=xl, mean=mean1, rstd=rstd1)
         ops.gemm(xl, fz.Wqkv, ops.EPI_BF16, qkv, bias=fz.bqkv, reserve_cus=reserve)
     del xl
-    if not _CLS_EARLY:
-        with fork.side():
-            probs, ta, t_pre, t_h, kv, crs = cls_chain(qkv, N)
     # lamda = cw / (cw + ow)  (:149-151,184-186,272; no grad): `ow` is a batched 197x197x768 GEMM reduced to (max, sum exp)
     # partials, independent of the class-token path and of the spatial attention (:264).  Fused form: kx, ready early on
     # the side stream, rides that GEMM as a 198th key, so `cw` comes out of the same launch (no separate pass over q).
-    fused = _LAMBDA_FUSED and _CLS_EARLY and N < 256 and ops.expsum_tiles(N, N) == 8
-    ss, part_ready = None, None
+    fused = N < 256 and ops.expsum_tiles(N, N) == 8
     if fused:
         fork.sync_main_to_side()          # kx
         nt = 16
@@ -532,31 +490,26 @@ def _block_forward(x, fz: _Frozen, adp: Dict[str, _AdapterW], B, T, N, H, dms1, 
         # N = 257 (ViT-L/14): the scores of tokens 0..255 against each other are ONE full tile per frame of the persistent
         # 256 x 256 kernel (8 slots); the 257th row and column and the cross scores come from one pass over q and k
         # (aim_qk_border: slots 8, 9).  Other N > 256 or N <= 128: the 128 x 128 kernel's tiles + qk_cross.
-        border = (_EXPSUM_BORDER and N == 257 and D in (512, 1024) and _LAMBDA_ON_SIDE and _CLS_EARLY
-                  and ops.expsum_tiles(N - 1, N - 1) == 8)      # (slots 8, 9 sit behind the one tile's 8)
+        border = N == 257 and D in (512, 1024) and ops.expsum_tiles(N - 1, N - 1) == 8      # (slots 8, 9 behind the tile's 8)
         nt = 10 if border else ops.expsum_tiles(N, N)
         part = _empty((BT, nt, 2), F32, dev)
         # the cross scores q_i . kx (one pass over q) go to the side stream as soon as q exists, beside the ow GEMM
-        if _LAMBDA_ON_SIDE and _CLS_EARLY:
-            fork.sync_side_to_main()
-            with fork.side():
-                ss = ar.take((BT, N), F32)
-                if border:
-                    ops.qk_border(qkv, kv, ss, part, 8, BT, N, D, 0.125)
-                else:
-                    ops.qk_cross(qkv, kv, ss, BT, N, D, 0.125)
-
-        def expsum():
+        fork.sync_side_to_main()
+        with fork.side():
+            ss = ar.take((BT, N), F32)
             if border:
-                ops.gemm(qkv, qkv[:, D:], ops.EPI_EXPSUM, part, M=N - 1, N=N - 1, K=D, batch=BT, stride_a=N * 3 * D,
-                         stride_w=N * 3 * D, scale=0.125, slot_stride=2 * nt)
+                ops.qk_border(qkv, kv, ss, part, 8, BT, N, D, 0.125)
             else:
-                ops.gemm(qkv, qkv[:, D:], ops.EPI_EXPSUM, part, M=N, N=N, K=D, batch=BT, stride_a=N * 3 * D,
-                         stride_w=N * 3 * D, scale=0.125)
-
-        part_ready = fork.run_beside(expsum) if _EXPSUM_DETACHED else expsum()
-
-    def lamda_chain():
+                ops.qk_cross(qkv, kv, ss, BT, N, D, 0.125)
+        if border:
+            ops.gemm(qkv, qkv[:, D:], ops.EPI_EXPSUM, part, M=N - 1, N=N - 1, K=D, batch=BT, stride_a=N * 3 * D,
+                     stride_w=N * 3 * D, scale=0.125, slot_stride=2 * nt)
+        else:
+            ops.gemm(qkv, qkv[:, D:], ops.EPI_EXPSUM, part, M=N, N=N, K=D, batch=BT, stride_a=N * 3 * D,
+                     stride_w=N * 3 * D, scale=0.125)
+    # the lamda chain needs `part`; it runs beside the spatial attention
+    fork.sync_side_to_main()
+    with fork.side():
         lam, oml = ar.take((BT,), F32), ar.take((BT,), F32)
         if fused:
             ops.lambda_partials(part, lam, oml, BT)
@@ -565,15 +518,7 @@ def _block_forward(x, fz: _Frozen, adp: Dict[str, _AdapterW], B, T, N, H, dms1, 
         # S_Adapter(lamda * crs_attn): a per-frame vector broadcast over tokens (:275)
         sin = ar.take((BT, D), BF16)
         ops.scale_rows(crs, lam, y=sin)
-        return (lam, oml, sin) + _adapter_fwd_small(sin, adp["S_Adapter"], BT, r, D, ar, out_f32=True)
-
-    if _LAMBDA_ON_SIDE:               # the chain runs beside the spatial attention instead of after it
-        if part_ready is not None:
-            fork.side_stream.wait_event(part_ready)      # it needs `part`
-        else:
-            fork.sync_side_to_main()
-        with fork.side():
-            lam, oml, sin, sv, s_pre, s_h = lamda_chain()
+        sv, s_pre, s_h = _adapter_fwd_small(sin, adp["S_Adapter"], BT, r, D, ar, out_f32=True)
     if f8 is not None:
         ao, lse = _empty((M, D), ops.FP8, dev), None
         ops.attn_fwd_fp8(qkv, ao, BT, N, H)
@@ -586,10 +531,6 @@ def _block_forward(x, fz: _Frozen, adp: Dict[str, _AdapterW], B, T, N, H, dms1, 
         lse = _empty((BT, H, N), F32, dev)
         ops.attn_fwd(qkv, ao, lse, BT, N, H)
     fork.join()
-    if not _LAMBDA_ON_SIDE:
-        if part_ready is not None:
-            torch.cuda.current_stream(dev).wait_event(part_ready)
-        lam, oml, sin, sv, s_pre, s_h = lamda_chain()
     # x1 = x + (1 - lamda) * out_proj(ao) + drop_path(scale * s_vec)
     H4 = 4 * D
     if f8 is not None:
@@ -764,7 +705,7 @@ def _block_backward(dyb, c, fz: _Frozen, adp: Dict[str, _AdapterW], grads, B, T,
     top = bool(c.get("top"))
     # sum_n dms1[n] * d(x1)[frame, n, :] (the per-frame S_Adapter vector's gradient) comes out of the ln_2 backward itself
     # (top form: the class row is the frame's only non-zero row of d(x1), so the sum is dms1[0] * that row)
-    fsum_in_ln = _FSUM_IN_LN and not top
+    fsum_in_ln = not top
     fpart = _empty((BT, ops.LN_FSUM_GROUPS, D), F32, dev) if fsum_in_ln else None
     # the big weight gradients whose rows ride in this block's dgrad launches (ops.WgradRide): what the MLP's two launches
     # left of them is offered to the out_proj and QKV dgrads below; their sums are finished behind the last of those
@@ -784,10 +725,8 @@ def _block_backward(dyb, c, fz: _Frozen, adp: Dict[str, _AdapterW], grads, B, T,
         dsv = ar.take((BT, D), F32)
         if fsum_in_ln:
             ops.frame_sum(fpart, None, dsv, BT, ops.LN_FSUM_GROUPS, D)      # the groups' partial sums, in order
-        elif top:
-            ops.frame_sum(dx1b, c["dms1"][:1], dsv, BT, 1, D)
         else:
-            ops.frame_sum(dx1b, c["dms1"], dsv, BT, N, D)
+            ops.frame_sum(dx1b, c["dms1"][:1], dsv, BT, 1, D)
         # S_Adapter on the per-frame vector sin = lamda * crs ; crs = (xt Wv^T + bv) Wo^T + bo
         dsv_b = ar.take((BT, D), BF16)
         ops.cast_bf16(dsv, dsv_b)
@@ -806,11 +745,10 @@ def _block_backward(dyb, c, fz: _Frozen, adp: Dict[str, _AdapterW], grads, B, T,
         ops.gemm(dta, fz.WoT, ops.EPI_BF16, dot)
         # the class rows' share of d(qkv) and its QKV dgrad stay on the side stream: the main stream's big dgrad GEMM
         # below does not wait for the class-token chain
-        if _LATE_JOIN:
-            dqkv_cls = ar.take((BT, 3 * D), BF16)
-            ops.cls_attn_bwd(c["qkv"], c["probs"], dot, dqkv_cls, B, T, N, H, compact=True)
-            dxl_cls = ar.take((BT, D), F32)
-            ops.gemm(dqkv_cls, fz.WqkvT, ops.EPI_F32, dxl_cls)
+        dqkv_cls = ar.take((BT, 3 * D), BF16)
+        ops.cls_attn_bwd(c["qkv"], c["probs"], dot, dqkv_cls, B, T, N, H, compact=True)
+        dxl_cls = ar.take((BT, D), F32)
+        ops.gemm(dqkv_cls, fz.WqkvT, ops.EPI_F32, dxl_cls)
     detached = keep is not None
     if keep is None:       # stand-alone use: the weight gradients are complete when this function returns
         keep = []
@@ -830,17 +768,13 @@ def _block_backward(dyb, c, fz: _Frozen, adp: Dict[str, _AdapterW], grads, B, T,
         delta = _empty((BT, H, N), F32, dev)
         ops.attn_bwd(c["qkv"], c["ao"], dao, c["lse"], delta, dqkv, BT, N, H)
     del dao
-    if not _LATE_JOIN:      # (A/B switch) join first and add the class rows into d(qkv) itself
-        fork.join()
-        ops.cls_attn_bwd(c["qkv"], c["probs"], dot, dqkv, B, T, N, H)
     dxl = _empty((M, D), BF16, dev)
     ops.gemm(dqkv, fz.WqkvT, ops.EPI_BF16, dxl, reserve_cus=_DP_RESERVE, ride=rides)
     del dqkv
     # the riders' slabs are complete behind this launch: the rows nobody took and the sums go beside the main stream
     _wgrads_beside(fork, [rd.finish for rd in rides], keep if detached else None)
-    if _LATE_JOIN:
-        fork.join()
-        ops.add_rows(dxl, N * D, dxl_cls)       # class rows: rows n == 0 of every frame
+    fork.join()
+    ops.add_rows(dxl, N * D, dxl_cls)       # class rows: rows n == 0 of every frame
     # ---- ln_1
     dxb = _empty((M, D), BF16, dev)
     if top:
