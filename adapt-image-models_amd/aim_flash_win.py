@@ -36,7 +36,6 @@ The reference's shifted branch (``not_shift=False``) rolls the windows back and 
 ``windows_attn``, ``:192`` rearranges ``shifted_win``): its output is mis-aligned by the shift.  It is not built.
 """
 import logging
-from types import SimpleNamespace
 from typing import Dict, List, Optional
 
 import torch
@@ -44,7 +43,7 @@ from torch import nn
 
 from . import ops
 from .backbone import (_AUX_GRAD, _DP_RESERVE, BF16, F32, Adapter, LayerNorm, QuickGELU, ViT_CLIP, _AdapterW, _embed_backward,
-                       _embed_forward, _empty, _Fork, _Frozen, _GradBufs, _ln_post_backward, _ln_post_forward,
+                       _clip_names, _embed_forward, _empty, _Fork, _Frozen, _GradBufs, _ln_post_backward, _ln_post_forward,
                        _mlp_adapter_backward, _mlp_adapter_forward, _wgrads_beside)
 from .registry import BACKBONES
 from .win_block import (check_win_clip, check_window, clip_window, from_slot_layout, to_slot_layout, win_prompt_grad,
@@ -100,10 +99,7 @@ class WinTransformer(nn.Module):
 
 def _frozen_view(blk: WinResidualAttentionBlock):
     """the block's frozen tensors under the names ``_Frozen`` reads (CLIP's nn.MultiheadAttention / c_fc / c_proj)"""
-    a = blk.attn
-    return SimpleNamespace(attn=SimpleNamespace(in_proj_weight=a.Wqkv.weight, in_proj_bias=a.Wqkv.bias, out_proj=a.out_proj),
-                           mlp=SimpleNamespace(c_fc=blk.mlp.fc1, c_proj=blk.mlp.fc2), ln_1=blk.ln_1, ln_2=blk.ln_2,
-                           d_model=blk.d_model, MLP_Adapter=blk.MLP_Adapter)
+    return _clip_names(blk, blk.attn.Wqkv, blk.attn.out_proj, blk.mlp.fc1, blk.mlp.fc2, blk.ln_1, blk.ln_2)
 
 
 def _block_forward(x, fz: _Frozen, adp: Dict[str, _AdapterW], B, T, N, P, H, window, f1, f2, f3, tokm, save: bool, shift=None):

@@ -15,6 +15,7 @@ import contextlib
 import logging
 import os
 from collections import OrderedDict
+from types import SimpleNamespace
 from typing import Dict, List, Optional
 
 import torch
@@ -85,6 +86,7 @@ class Transformer(nn.Module):
 
 
 _ADAPTERS = ("MLP_Adapter", "S_Adapter", "T_Adapter")
+_SMALL_ADAPTERS = ("S_Adapter", "T_Adapter", "T_Adapter_in")      # T_Adapter_in: ViT_ImageNet(num_tadapter=2) only
 _ADAPTER_LEAVES = ("D_fc1.weight", "D_fc1.bias", "D_fc2.weight", "D_fc2.bias")
 
 
@@ -99,17 +101,27 @@ def _cast(w: torch.Tensor, transpose: bool = False) -> torch.Tensor:
     return out
 
 
+def _clip_names(blk, qkv, proj, fc1, fc2, ln_1, ln_2):
+    """A block whose containers carry other names (flash_attn's, timm's) under the names ``_Frozen`` and
+    ``fp32_path._Block32`` read: CLIP's nn.MultiheadAttention / c_fc / c_proj / ln_1 / ln_2, and the adapters it has."""
+    return SimpleNamespace(attn=SimpleNamespace(in_proj_weight=qkv.weight, in_proj_bias=qkv.bias, out_proj=proj),
+                           mlp=SimpleNamespace(c_fc=fc1, c_proj=fc2), ln_1=ln_1, ln_2=ln_2,
+                           **{n: getattr(blk, n) for n in ("MLP_Adapter",) + _SMALL_ADAPTERS if hasattr(blk, n)})
+
+
 class _Frozen:
-    """bf16 copies (and transposes, for dgrad) of one block's frozen weights; built once."""
+    """bf16 copies (and transposes, for dgrad) of one block's frozen weights; built once.  The only builder of bf16 block
+    operands: a block with other parameter names is handed in through ``_clip_names``."""
 
     def __init__(self, blk: ResidualAttentionBlock):
         a = blk.attn
+        self.eps = float(blk.ln_1.eps)
         self.Wqkv, self.WqkvT = _cast(a.in_proj_weight), _cast(a.in_proj_weight, True)
         self.Wo, self.WoT = _cast(a.out_proj.weight), _cast(a.out_proj.weight, True)
         # Frozen MLP and the trainable MLP_Adapter share their GEMMs (same input xn, outputs summed): the
         # operands are concatenated once -- [W_fc ; D_fc1] along N, [W_proj | D_fc2] along K -- and only the
         # adapter slices are re-cast each step (stage_mlp_adapter).  Both orientations for fwd and dgrad.
-        D = blk.d_model
+        D = blk.ln_1.normalized_shape[0]
         r = blk.MLP_Adapter.D_fc1.weight.shape[0]
         dev = a.in_proj_weight.device
         self.D, self.r, self.H4 = D, r, 4 * D
@@ -124,12 +136,14 @@ class _Frozen:
         ops.cast_bf16(wfc, self.WcatT1[:, :4 * D], transpose=True)
         self.bcat1 = torch.zeros(4 * D + r, dtype=F32, device=dev)
         self.bcat1[:4 * D] = blk.mlp.c_fc.bias.detach().float()
-        # bf16 operands of the two small adapters (re-cast every step by the model's cast table)
-        self.small = {a: dict(W1=torch.empty((r, D), dtype=BF16, device=dev), W1T=torch.empty((D, r), dtype=BF16, device=dev),
+        # bf16 operands of the small adapters the block has (re-cast every step by the model's cast table)
+        self.small = {n: dict(W1=torch.empty((r, D), dtype=BF16, device=dev), W1T=torch.empty((D, r), dtype=BF16, device=dev),
                               W2=torch.empty((D, r), dtype=BF16, device=dev), W2T=torch.empty((r, D), dtype=BF16, device=dev))
-                      for a in ("S_Adapter", "T_Adapter")}
+                      for n in _SMALL_ADAPTERS if hasattr(blk, n)}
         f = lambda p: p.detach().float().contiguous()
-        self.bqkv, self.bo = f(a.in_proj_bias), f(a.out_proj.bias)
+        # (a fused QKV projection without bias gets a zero vector: the kernels always add one)
+        self.bqkv = f(a.in_proj_bias) if a.in_proj_bias is not None else torch.zeros(3 * D, dtype=F32, device=dev)
+        self.bo = f(a.out_proj.bias)
         self.bpr = f(blk.mlp.c_proj.bias)
         self.g1, self.b1 = f(blk.ln_1.weight), f(blk.ln_1.bias)
         self.g2, self.b2 = f(blk.ln_2.weight), f(blk.ln_2.bias)

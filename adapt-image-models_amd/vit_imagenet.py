@@ -16,6 +16,9 @@ parameter names and shapes, ``init_weights`` policy (nothing is frozen) and ``fo
   ``requires_grad`` is False gets ``None`` and costs no launch.
 
 Every GEMM weight gradient uses the split-M, fixed-order ``aim_wgrad_bias_bf16``; the step is bitwise reproducible.
+
+The block's bf16 operands are ``backbone._Frozen``'s, which reads the timm-named block through ``_frozen_view``; the fp32 mode
+(vit_imagenet_fp32.py) reads it through the same view and runs the one fp32 AIM-style block of fp32_path.py.
 """
 import functools
 import logging
@@ -25,7 +28,8 @@ import torch
 from torch import nn
 
 from . import ops
-from .backbone import BF16, F32, _AUX_FRAG, _AUX_GRAD, _AdapterW, _Frozen, _conv_operand, _empty, _cast
+from .backbone import (BF16, F32, _AUX_FRAG, _AUX_GRAD, _SMALL_ADAPTERS as _SMALL, _AdapterW, _Frozen, _clip_names, _conv_operand,
+                       _empty)
 from .registry import BACKBONES
 
 _LOG = logging.getLogger("aim_amd")
@@ -89,42 +93,12 @@ class PatchEmbed(nn.Module):
         self.proj = nn.Conv2d(in_chans, embed_dim, kernel_size=patch_size, stride=patch_size, bias=bias)
 
 
-_SMALL = ("S_Adapter", "T_Adapter", "T_Adapter_in")
 _ADAPTERS = ("MLP_Adapter",) + _SMALL
 
 
-class _FrozenIN(_Frozen):
-    """bf16 operands of one block's frozen-size weights (``_Frozen``'s layout: fused QKV, ``[fc1 ; D_fc1]`` / ``[fc2 | D_fc2]``
-    concatenations, both orientations) from the timm-named parameters; a ``qkv`` without bias gets a zero bias vector."""
-
-    def __init__(self, blk: Block):  # noqa: super().__init__ reads the CLIP names
-        a, D = blk.attn, blk.norm1.normalized_shape[0]
-        r = blk.MLP_Adapter.D_fc1.weight.shape[0]
-        dev = a.qkv.weight.device
-        self.D, self.r, self.H4 = D, r, 4 * D
-        self.eps = float(blk.norm1.eps)
-        self.Wqkv, self.WqkvT = _cast(a.qkv.weight), _cast(a.qkv.weight, True)
-        self.Wo, self.WoT = _cast(a.proj.weight), _cast(a.proj.weight, True)
-        self.Wcat1 = torch.empty((4 * D + r, D), dtype=BF16, device=dev)
-        self.Wcat2 = torch.empty((D, 4 * D + r), dtype=BF16, device=dev)
-        self.WcatT2 = torch.empty((4 * D + r, D), dtype=BF16, device=dev)
-        self.WcatT1 = torch.empty((D, 4 * D + r), dtype=BF16, device=dev)
-        wfc, wpr = blk.mlp.fc1.weight.detach().float().contiguous(), blk.mlp.fc2.weight.detach().float().contiguous()
-        ops.cast_bf16(wfc, self.Wcat1[:4 * D])
-        ops.cast_bf16(wpr, self.Wcat2[:, :4 * D])
-        ops.cast_bf16(wpr, self.WcatT2[:4 * D], transpose=True)
-        ops.cast_bf16(wfc, self.WcatT1[:, :4 * D], transpose=True)
-        self.bcat1 = torch.zeros(4 * D + r, dtype=F32, device=dev)
-        self.bcat1[:4 * D] = blk.mlp.fc1.bias.detach().float()
-        self.small = {n: dict(W1=torch.empty((r, D), dtype=BF16, device=dev), W1T=torch.empty((D, r), dtype=BF16, device=dev),
-                              W2=torch.empty((D, r), dtype=BF16, device=dev), W2T=torch.empty((r, D), dtype=BF16, device=dev))
-                      for n in _SMALL if hasattr(blk, n)}
-        f = lambda p: p.detach().float().contiguous()
-        self.bqkv = f(a.qkv.bias) if a.qkv.bias is not None else torch.zeros(3 * D, dtype=F32, device=dev)
-        self.bo = f(a.proj.bias)
-        self.bpr = f(blk.mlp.fc2.bias)
-        self.g1, self.b1 = f(blk.norm1.weight), f(blk.norm1.bias)
-        self.g2, self.b2 = f(blk.norm2.weight), f(blk.norm2.bias)
+def _frozen_view(blk: Block):
+    """the block's tensors under the names ``_Frozen`` and ``fp32_path._Block32`` read (as ``aim_flash_win._frozen_view``)"""
+    return _clip_names(blk, blk.attn.qkv, blk.attn.proj, blk.mlp.fc1, blk.mlp.fc2, blk.norm1, blk.norm2)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -143,7 +117,7 @@ def _adapter_skip_fwd(xin, ad: _AdapterW, M, r, D):
     return yb, pre, h
 
 
-def _block_forward(x, fz: _FrozenIN, adp: Dict[str, _AdapterW], B, T, N, H, dp1, dms2, save: bool, keep: Dict[str, bool]):
+def _block_forward(x, fz: _Frozen, adp: Dict[str, _AdapterW], B, T, N, H, dp1, dms2, save: bool, keep: Dict[str, bool]):
     """x: [B*T*N, D] f32 -> x3.  ``dp1`` [B*T]: the temporal branch's per-frame DropPath factor (:121); ``dms2`` [B*T]: the
     MLP_Adapter's, times ``scale`` (:125).  ``keep``: which frozen-size weights need gradients (their operands are saved)."""
     dev = x.device
@@ -210,7 +184,7 @@ def _block_forward(x, fz: _FrozenIN, adp: Dict[str, _AdapterW], B, T, N, H, dp1,
     return x3, ctx
 
 
-def _block_backward(dyb, c, fz: _FrozenIN, adp: Dict[str, _AdapterW], gr: Dict[str, Optional[torch.Tensor]], B, T, N, H):
+def _block_backward(dyb, c, fz: _Frozen, adp: Dict[str, _AdapterW], gr: Dict[str, Optional[torch.Tensor]], B, T, N, H):
     """dyb = d(loss)/d(x3) [M, D] bf16 -> d(loss)/d(x) bf16.  ``gr``: this block's fp32 gradient buffers by parameter name
     under ``blocks.{i}.`` (missing = not wanted); every kernel ACCUMULATES into them."""
     dev = dyb.device
@@ -559,7 +533,7 @@ class ViT_ImageNet(nn.Module):
         f = lambda t: t.detach().float().contiguous()
         out = dict(conv=_conv_operand(w), conv_b=f(b) if b is not None else torch.zeros(D, dtype=F32, device=w.device),
                    cls=f(self.cls_token).view(D), pos=f(self.pos_embed).view(-1, D),
-                   blocks=[_FrozenIN(blk) for blk in self.blocks])
+                   blocks=[_Frozen(_frozen_view(blk)) for blk in self.blocks])
         self._frozen_cache = (key, out)
         self._cast_table = None
         return out
@@ -640,7 +614,7 @@ class ViT_ImageNet(nn.Module):
                 y = _ViTImageNetFn32.apply(self, x, *params)
             else:
                 with torch.no_grad():
-                    y = forward_f32(self, x, dict(zip(self._param_names(), params)), save=False)[0]
+                    y = forward_f32(self, x, dict(zip(self._param_names(), params)), ())[0]
             return y.unsqueeze(-1).unsqueeze(-1)
         y = _ViTImageNetFn.apply(self, torch.is_grad_enabled(), x, *params)      # [B, D, T]
         return y.unsqueeze(-1).unsqueeze(-1)
