@@ -44,6 +44,16 @@ class WgradRideArgs(Structure):
     ]
 
 
+class LowrankArgs(Structure):
+    """Mirror of ``aim_lowrank_args``."""
+    _fields_ = [
+        ("x", c_void_p * 3), ("ldx", c_int32), ("wa", c_void_p * 3), ("ba", c_void_p * 3), ("h", c_void_p * 3),
+        ("ldh", c_int32), ("wb", c_void_p * 3), ("bb", c_void_p * 3), ("y", c_void_p * 3), ("ldy", c_int32),
+        ("y32", c_void_p), ("resid", c_void_p), ("ld32", c_int32), ("ldr", c_int32),
+        ("M", c_int32), ("D", c_int32), ("r", c_int32), ("G", c_int32), ("alpha", c_float),
+    ]
+
+
 P = c_void_p
 I = c_int
 L = c_int64
@@ -88,6 +98,8 @@ SIGNATURES = {
     "aim_tattn_bwd": [P, P, P, P, I, I, I, I, P],
     "aim_add_bf16": [P, L, P, L, P, L, I, I, P],
     "aim_acc_bf16": [P, P, L, I, I, P],
+    "aim_lowrank_fwd": [POINTER(LowrankArgs), P],
+    "aim_lowrank_bwd": [POINTER(LowrankArgs), P],
     "aim_lambda_partials": [P, P, P, I, P],
     "aim_qk_cross": [P, P, I, P, I, I, I, F, P],
     "aim_lambda": [P, P, I, P, P, I, P, P, I, I, I, F, P],
@@ -129,7 +141,7 @@ SIGNATURES = {
     "aim_layernorm_gb_bwd": [P, I, L, P, L, P, P, P, P, I, I, P, L, P],
 }
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 
 def load_library():

@@ -8,7 +8,7 @@ from typing import Optional
 
 import torch
 
-from .lib import GemmArgs, WgradRideArgs, check, load_library
+from .lib import GemmArgs, LowrankArgs, WgradRideArgs, check, load_library
 
 EPI_BF16, EPI_ACT, EPI_DACT, EPI_F32, EPI_EXPSUM, EPI_ACT8, EPI_RES16 = 0, 1, 2, 3, 4, 5, 6
 FP8 = torch.float8_e4m3fn          # OCP e4m3 (gfx950); stored as bytes
@@ -563,6 +563,62 @@ def acc_bf16(x, s):
     assert x.is_contiguous() and x.shape == s.shape
     check(load_library().aim_acc_bf16(x.data_ptr(), s.data_ptr(), s.stride(0), x.shape[0], x.shape[1], _stream()), "aim_acc_bf16")
     return x
+
+
+def _lowrank_args(xs, wa, ba, hs, wb, bb, ys, alpha, y32=None, resid=None) -> LowrankArgs:
+    """``aim_lowrank_args`` of G = len(wa) adapters; every list entry of hs / ys / ba / bb may be None"""
+    G = len(wa)
+    r, D = wa[0].shape
+    for t in list(xs) + list(wa) + list(wb) + list(hs) + list(ys):
+        _chk(t, BF16, "lowrank operand")
+    for t in list(ba) + list(bb) + [y32, resid]:
+        _chk(t, F32, "lowrank bias / fp32 operand")
+    for w in list(wa) + list(wb):
+        if not w.is_contiguous():
+            raise ValueError("lowrank: the weights must be dense")
+    if any(tuple(w.shape) != (r, D) for w in wa) or any(tuple(w.shape) != (D, r) for w in wb):
+        raise ValueError("lowrank: the first weights must be [r, D] and the second [D, r], the same for every adapter")
+
+    def one_stride(ts, what):
+        s = {t.stride(0) for t in ts if t is not None}
+        if len(s) > 1:
+            raise ValueError(f"lowrank: every {what} must have the same row stride")
+        return s.pop() if s else max(D, r)
+
+    a = LowrankArgs()
+    M = xs[0].shape[0]
+    for g in range(G):
+        a.x[g] = _p(xs[g]) if g < len(xs) else None
+        a.wa[g], a.wb[g] = wa[g].data_ptr(), wb[g].data_ptr()
+        a.ba[g], a.bb[g] = _p(ba[g]), _p(bb[g])
+        a.h[g], a.y[g] = _p(hs[g]), (_p(ys[g]) if g < len(ys) else None)
+    a.ldx, a.ldh, a.ldy = one_stride(xs, "input"), one_stride(hs, "intermediate"), one_stride(ys, "output")
+    a.y32, a.resid = _p(y32), _p(resid)
+    a.ld32 = y32.stride(0) if y32 is not None else 0
+    a.ldr = resid.stride(0) if resid is not None else 0
+    a.M, a.D, a.r, a.G, a.alpha = M, D, r, G, float(alpha)
+    return a
+
+
+def lowrank_fwd(x, w1, b1, w2, b2, *, h=None, y=None, alpha: float = 1.0, y32=None, resid=None):
+    """G fused linear bottleneck adapters on one input (``aim_lowrank_fwd``; G = len(w1) in {1, 3}):
+    ``h[g] = bf16(x w1[g]^T + b1[g])`` (stored where ``h[g]`` is given), ``y[g] = alpha x + h[g] w2[g]^T + b2[g]``.  x [M, D]
+    bf16 and every y[g] may be row-strided; w1[g] [r, D], w2[g] [D, r] bf16 dense; biases fp32.  G == 1: ``y32 = resid + `` the
+    same sum before its rounding (fp32), beside or instead of y[0]."""
+    G = len(w1)
+    h = [None] * G if h is None else list(h)
+    y = [None] * G if y is None else list(y)
+    a = _lowrank_args([x], w1, b1, h, w2, b2, y, alpha, y32, resid)
+    check(load_library().aim_lowrank_fwd(byref(a), _stream()), "aim_lowrank_fwd")
+
+
+def lowrank_bwd(dy, w2t, w1t, dh, dx, *, alpha: float = 1.0):
+    """Backward of ``lowrank_fwd`` towards its input (``aim_lowrank_bwd``): ``dh[g] = bf16(dy[g] w2[g])`` from the transposed
+    copy w2t[g] [r, D], ``dx = bf16(alpha sum_g dy[g] + sum_g dh[g] w1[g])`` from w1t[g] [D, r].  The dy[g] share one row stride
+    (column slabs of one buffer); every dh[g] is an output."""
+    G = len(w2t)
+    a = _lowrank_args(list(dy), w2t, [None] * G, list(dh), w1t, [None] * G, [dx], alpha)
+    check(load_library().aim_lowrank_bwd(byref(a), _stream()), "aim_lowrank_bwd")
 
 
 def lambda_partials(partials, lam, one_minus, BT):

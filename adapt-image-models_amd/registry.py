@@ -143,6 +143,8 @@ def register_into_mmaction() -> bool:
     MB.register_module(name="AIM_FLASH_WIN", force=True, module=AIM_FLASH_WIN)     # vitclip_aim_flash_win.py:276, wind_attn=True
     from .aim_flash import AIM_FLASH
     MB.register_module(name="AIM_FLASH", force=True, module=AIM_FLASH)             # vitclip_aim_flash.py:402, wind_attn=True
+    from .zeroi2v import ViT_CLIP_ZEROI2V
+    MB.register_module(name="ViT_CLIP_ZEROI2V", force=True, module=ViT_CLIP_ZEROI2V)       # vit_clip_zeroI2V.py:361
     return True
 
 

@@ -1,7 +1,8 @@
 """``ViT_CLIP_ZEROI2V`` backbone (ZeroI2V: CLIP ViT + adapters + head-shifted spatial attention) on the HIP kernels.
 
-Drop-in for ``mmaction/models/backbones/vit_clip_zeroI2V.py:361-509`` of the reference at ``linear_adapter=False`` (what its
-three recipes use): same registry name, constructor keywords, ``init_weights`` policy and parameter names / shapes as
+Drop-in for ``mmaction/models/backbones/vit_clip_zeroI2V.py:361-509`` of the reference.  This file: the class, and the block at
+``linear_adapter=False`` (what its three recipes use); the block with the linear adapters, and their fold into the frozen
+weights, are in zeroi2v_linear.py.  Same registry name, constructor keywords, ``init_weights`` policy and parameter names / shapes as
 ``ViT_CLIP`` (``T_Adapter`` exists only with ``with_t_cls_token=True``), same ``forward(x[B,3,T,H,W]) -> [B,width,T,1,1]``.
 
 Per block (reference ``:244-311``), frame-major rows, P = N + 1 tokens per frame with the temporal class token, else N:
@@ -27,8 +28,10 @@ import logging
 from typing import Dict, List, Optional
 
 import torch
+from torch import nn
 
 from . import ops
+from . import zeroi2v_linear as lin
 from .backbone import (_AUX_GRAD, _DP_RESERVE, BF16, F32, ViT_CLIP, _AdapterW, _Arena, _embed_backward, _embed_forward, _empty,
                        _Fork, _Frozen, _GradBufs, _ln_post_backward, _ln_post_forward, _mlp_adapter_backward,
                        _mlp_adapter_forward, _wgrads_beside)
@@ -48,6 +51,55 @@ def head_shifts(T: int, H: int):
     return tuple(tab) + (0,) * (H - len(tab))
 
 
+def _cls_chain_forward(x, fz, ad, B, T, P, H):
+    """The temporal class token (both adapter modes): ln_1 + QKV of the class rows, attention over the T frames of each clip,
+    out_proj (the block's frozen, un-adapted ``fz.Wqkv`` / ``fz.Wo``), then the T_Adapter ``ad``, whose up-projection writes xt
+    into row 1 of every frame of x.  Returns what ``_cls_chain_backward`` reads."""
+    dev = x.device
+    D = x.shape[1]
+    BT, r = B * T, ad.W1.shape[0]
+    ar = _Arena(dev, 24 * BT * D + 4 * B * H * T * T + (1 << 16))
+    xl_cls = ar.take((BT, D), BF16)
+    ops.layernorm_fwd(x, fz.g1, fz.b1, BT, D, P * D, y_bf16=xl_cls, mean=ar.take((BT,), F32), rstd=ar.take((BT,), F32))
+    qkv_cls = ar.take((BT, 3 * D), BF16)
+    ops.gemm(xl_cls, fz.Wqkv, ops.EPI_BF16, qkv_cls, bias=fz.bqkv)
+    ot, probs = ar.take((BT, D), BF16), ar.take((B, H, T, T), F32)
+    ops.cls_attn_fwd(qkv_cls, ot, probs, B, T, 1, H)            # "N = 1": the rows ARE the class tokens
+    ta = ar.take((BT, D), BF16)
+    ops.gemm(ot, fz.Wo, ops.EPI_BF16, ta, bias=fz.bo)
+    t_pre, t_h = ar.take((BT, r), BF16), ar.take((BT, r), BF16)
+    ops.gemm(ta, ad.W1, ops.EPI_ACT, t_h, bias=ad.b1, out2=t_pre, act=ops.ACT_GELU, aux_grad=_AUX_GRAD)
+    ops.gemm(t_h, ad.W2, ops.EPI_F32, x.view(BT, P * D)[:, D:2 * D], bias=ad.b2)
+    return dict(qkv_cls=qkv_cls, probs=probs, ta=ta, t_pre=t_pre, t_h=t_h)
+
+
+def _cls_chain_backward(dxl, c, fz, ad, gt, later: list, B, T, P, H):
+    """d(xt) = row 1 of ln_1's backward (nothing else reaches it: row 1 of d(x'1) is zero); through the T_Adapter chain it
+    becomes one more gradient of the class rows' ln_1 output, added to ``dxl`` before the full-row ln_1 backward.  The
+    T_Adapter's weight-gradient closures are appended to ``later``."""
+    dev = dxl.device
+    D = dxl.shape[1]
+    BT, r = B * T, ad.W1.shape[0]
+    ar = _Arena(dev, 24 * BT * D + (1 << 16))
+    mean1s, rstd1s = c["mean1"].view(BT, P)[:, 1].contiguous(), c["rstd1"].view(BT, P)[:, 1].contiguous()
+    dxt = ar.take((BT, D), BF16)
+    ops.layernorm_bwd(dxl[1:], c["x"][1:], fz.g1, mean1s, rstd1s, BT, D, lddy=P * D, ldx=P * D, lddx=D, dx_bf16=dxt)
+    t_h, ta = c["t_h"], c["ta"]
+    later.append(lambda: ops.wgrad(dxt, t_h, gt["D_fc2.weight"], gt["D_fc2.bias"]))
+    dtp = ar.take((BT, r), BF16)
+    ops.gemm(dxt, ad.W2T, ops.EPI_DACT, dtp, aux=c["t_pre"], act=ops.ACT_GELU, aux_grad=_AUX_GRAD)
+    later.append(lambda: ops.wgrad(dtp, ta, gt["D_fc1.weight"], gt["D_fc1.bias"]))
+    dta = ar.take((BT, D), BF16)
+    ops.gemm(dtp, ad.W1T, ops.EPI_BF16, dta)
+    dot = ar.take((BT, D), BF16)
+    ops.gemm(dta, fz.WoT, ops.EPI_BF16, dot)
+    dqkv_cls = ar.take((BT, 3 * D), BF16)
+    ops.cls_attn_bwd(c["qkv_cls"], c["probs"], dot, dqkv_cls, B, T, 1, H, compact=True)
+    dxl_cls = ar.take((BT, D), F32)
+    ops.gemm(dqkv_cls, fz.WqkvT, ops.EPI_F32, dxl_cls)
+    ops.add_rows(dxl, P * D, dxl_cls)            # class rows: row 0 of every frame
+
+
 def _block_forward(x, fz: _Frozen, adp: Dict[str, _AdapterW], B, T, P, H, tcls: bool, shifts, dms1, dms2, save: bool):
     """x [B*T*P, D] f32 (row 1 of every frame: the slot of the temporal class token) -> x2, ctx.  dms1 / dms2: [P] DropPath
     factor times adapter scale per token (dms2[1] = 0 with the slot)."""
@@ -56,22 +108,7 @@ def _block_forward(x, fz: _Frozen, adp: Dict[str, _AdapterW], B, T, P, H, tcls: 
     BT, r = B * T, fz.r
     c: dict = {}
     if tcls:
-        # temporal class token: ln_1 + QKV of the class rows, attention over the T frames of each clip, out_proj, T_Adapter
-        # whose up-projection writes xt into row 1 of every frame
-        ar = _Arena(dev, 24 * BT * D + 4 * B * H * T * T + (1 << 16))
-        xl_cls = ar.take((BT, D), BF16)
-        ops.layernorm_fwd(x, fz.g1, fz.b1, BT, D, P * D, y_bf16=xl_cls, mean=ar.take((BT,), F32), rstd=ar.take((BT,), F32))
-        qkv_cls = ar.take((BT, 3 * D), BF16)
-        ops.gemm(xl_cls, fz.Wqkv, ops.EPI_BF16, qkv_cls, bias=fz.bqkv)
-        ot, probs = ar.take((BT, D), BF16), ar.take((B, H, T, T), F32)
-        ops.cls_attn_fwd(qkv_cls, ot, probs, B, T, 1, H)            # "N = 1": the rows ARE the class tokens
-        ta = ar.take((BT, D), BF16)
-        ops.gemm(ot, fz.Wo, ops.EPI_BF16, ta, bias=fz.bo)
-        ad = adp["T_Adapter"]
-        t_pre, t_h = ar.take((BT, r), BF16), ar.take((BT, r), BF16)
-        ops.gemm(ta, ad.W1, ops.EPI_ACT, t_h, bias=ad.b1, out2=t_pre, act=ops.ACT_GELU, aux_grad=_AUX_GRAD)
-        ops.gemm(t_h, ad.W2, ops.EPI_F32, x.view(BT, P * D)[:, D:2 * D], bias=ad.b2)
-        c.update(qkv_cls=qkv_cls, probs=probs, ta=ta, t_pre=t_pre, t_h=t_h)
+        c.update(_cls_chain_forward(x, fz, adp["T_Adapter"], B, T, P, H))
     # ln_1 and the QKV projection over every row
     xl = _empty((M, D), BF16, dev)
     mean1, rstd1 = _empty((M,), F32, dev), _empty((M,), F32, dev)
@@ -136,27 +173,7 @@ def _block_backward(dyb, c, fz: _Frozen, adp: Dict[str, _AdapterW], grads, B, T,
     ops.gemm(dqkv, fz.WqkvT, ops.EPI_BF16, dxl, reserve_cus=_DP_RESERVE)
     del dqkv
     if tcls:
-        # d(xt) = row 1 of ln_1's backward (nothing else reaches it: row 1 of d(x'1) is zero); through the T_Adapter chain it
-        # becomes one more gradient of the class rows' ln_1 output, added before the full-row ln_1 backward
-        ar = _Arena(dev, 24 * BT * D + (1 << 16))
-        mean1s, rstd1s = c["mean1"].view(BT, P)[:, 1].contiguous(), c["rstd1"].view(BT, P)[:, 1].contiguous()
-        dxt = ar.take((BT, D), BF16)
-        ops.layernorm_bwd(dxl[1:], c["x"][1:], fz.g1, mean1s, rstd1s, BT, D, lddy=P * D, ldx=P * D, lddx=D, dx_bf16=dxt)
-        ad, gt = adp["T_Adapter"], grads["T_Adapter"]
-        t_h, ta = c["t_h"], c["ta"]
-        later.append(lambda: ops.wgrad(dxt, t_h, gt["D_fc2.weight"], gt["D_fc2.bias"]))
-        dtp = ar.take((BT, r), BF16)
-        ops.gemm(dxt, ad.W2T, ops.EPI_DACT, dtp, aux=c["t_pre"], act=ops.ACT_GELU, aux_grad=_AUX_GRAD)
-        later.append(lambda: ops.wgrad(dtp, ta, gt["D_fc1.weight"], gt["D_fc1.bias"]))
-        dta = ar.take((BT, D), BF16)
-        ops.gemm(dtp, ad.W1T, ops.EPI_BF16, dta)
-        dot = ar.take((BT, D), BF16)
-        ops.gemm(dta, fz.WoT, ops.EPI_BF16, dot)
-        dqkv_cls = ar.take((BT, 3 * D), BF16)
-        ops.cls_attn_bwd(c["qkv_cls"], c["probs"], dot, dqkv_cls, B, T, 1, H, compact=True)
-        dxl_cls = ar.take((BT, D), F32)
-        ops.gemm(dqkv_cls, fz.WqkvT, ops.EPI_F32, dxl_cls)
-        ops.add_rows(dxl, P * D, dxl_cls)            # class rows: row 0 of every frame
+        _cls_chain_backward(dxl, c, fz, adp["T_Adapter"], grads["T_Adapter"], later, B, T, P, H)
     dxb = _empty((M, D), BF16, dev)
     ops.layernorm_bwd(dxl, c["x"], fz.g1, c["mean1"], c["rstd1"], M, D, lddy=D, ldx=D, lddx=D, dres=dres, dx_bf16=dxb)
     if tcls:
@@ -182,7 +199,9 @@ class _ZeroI2VFn(torch.autograd.Function):
         temporal, lnp_w, lnp_b = params[0], params[1], params[2]
         need_grad = grad_enabled and any(ctx.needs_input_grad)
         frozen = model._frozen_operands()
-        adp = model._stage_adapters(frozen, params)
+        linear, share = model.linear_adapter, model.share_adapter
+        merged = model._merged_operands() if (linear and model.merged) else None     # (forward() refused merged + gradients)
+        adp = model._stage_adapters(frozen, params) if merged is None else None
         # patch embedding, class token, positional / temporal embeddings, ln_pre: ViT_CLIP's kernels, N tokens per frame
         tok, x0, mean0, rstd0, tmp = _embed_forward(model, frozen, imgs, temporal)
         if tcls:        # once per forward: into the P-token layout (row 1 = the temporal class token's slot)
@@ -196,13 +215,20 @@ class _ZeroI2VFn(torch.autograd.Function):
         if model.inference_precision == 'fp8' and not need_grad and not model._fp8_warned:
             model._fp8_warned = True
             _LOG.warning("fp8 inference was requested but ViT_CLIP_ZEROI2V has no fp8 path: this forward runs bf16")
-        dp1, dp2 = model._drop_masks_z(P, N, model.training, dev)          # [L, P], [L, N]
-        if tcls:
-            dp2 = torch.cat([dp2[:, :1], torch.zeros_like(dp2[:, :1]), dp2[:, 1:]], dim=1).contiguous()
+        if not linear:      # (the linear mode has no DropPath and no adapter scale)
+            dp1, dp2 = model._drop_masks_z(P, N, model.training, dev)          # [L, P], [L, N]
+            if tcls:
+                dp2 = torch.cat([dp2[:, :1], torch.zeros_like(dp2[:, :1]), dp2[:, 1:]], dim=1).contiguous()
         shifts = model.head_shifts
         ctxs: List[Optional[dict]] = []
         for i in range(L):
-            x, c = _block_forward(x, frozen["blocks"][i], adp[i], B, T, P, H, tcls, shifts, dp1[i], dp2[i], need_grad)
+            fz = frozen["blocks"][i]
+            if merged is not None:
+                x, c = lin.merged_block_forward(x, fz, merged[i], B, T, P, H, tcls, shifts, _cls_chain_forward), None
+            elif linear:
+                x, c = lin.block_forward(x, fz, adp[i], B, T, P, H, tcls, share, shifts, need_grad, _cls_chain_forward)
+            else:
+                x, c = _block_forward(x, fz, adp[i], B, T, P, H, tcls, shifts, dp1[i], dp2[i], need_grad)
             ctxs.append(c)
         y, gw, meanp, rstdp = _ln_post_forward(x, lnp_w, lnp_b, BT, P)
         if need_grad:
@@ -227,8 +253,12 @@ class _ZeroI2VFn(torch.autograd.Function):
         dxb = _ln_post_backward(dy, s, dgw, dgb, BT, P)
         keep: list = []
         for i in reversed(range(L)):
-            dxb = _block_backward(dxb, s["ctxs"][i], frozen["blocks"][i], s["adp"][i], layer_grads[i], B, T, P, H, tcls,
-                                  s["shifts"], keep)
+            if model.linear_adapter:
+                dxb = lin.block_backward(dxb, s["ctxs"][i], frozen["blocks"][i], s["adp"][i], layer_grads[i], B, T, P, H, tcls,
+                                         model.share_adapter, s["shifts"], keep, _cls_chain_backward)
+            else:
+                dxb = _block_backward(dxb, s["ctxs"][i], frozen["blocks"][i], s["adp"][i], layer_grads[i], B, T, P, H, tcls,
+                                      s["shifts"], keep)
             s["ctxs"][i] = None
             gbufs.layer_ready(i)
         if tcls:        # once per backward: back to the embedding's N tokens per frame (the slot's row is zero)
@@ -249,9 +279,10 @@ class ViT_CLIP_ZEROI2V(ViT_CLIP):
     def __init__(self, input_resolution: int, num_frames: int, patch_size: int, width: int, layers: int, heads: int,
                  drop_path_rate, num_tadapter=1, adapter_scale=0.5, with_t_cls_token=False, share_adapter=False,
                  bottleneck=192, linear_adapter=False, pretrained=None):
-        if linear_adapter:
-            raise NotImplementedError("ViT_CLIP_ZEROI2V(linear_adapter=True): the linear adapters (Attn_Adapter_*, "
-                                      "MLP_Adapter_in / _out) and their re-parameterisation are not built")
+        if linear_adapter and (bottleneck % 8 != 0 or not 8 <= bottleneck <= min(width, lin.MAX_BOTTLENECK)):
+            raise NotImplementedError(f"ViT_CLIP_ZEROI2V(linear_adapter=True, bottleneck={bottleneck}, width={width}): the fused "
+                                      f"low-rank kernels of the linear adapters take a bottleneck that is a multiple of 8, at "
+                                      f"most the width and at most {lin.MAX_BOTTLENECK}")
         if num_tadapter == 2 and with_t_cls_token:
             # reference :253 calls attention() with one argument: TypeError at the first forward
             raise TypeError("ViT_CLIP_ZEROI2V(num_tadapter=2, with_t_cls_token=True): the reference's block fails with "
@@ -260,14 +291,67 @@ class ViT_CLIP_ZEROI2V(ViT_CLIP):
                          adapter_scale=adapter_scale, pretrained=pretrained)
         self.num_tadapter = num_tadapter
         self.with_t_cls_token = bool(with_t_cls_token)
-        self.share_adapter, self.bottleneck, self.linear_adapter = share_adapter, bottleneck, linear_adapter   # linear adapters only
-        if not self.with_t_cls_token:       # reference :109-110: the T_Adapter exists only with the temporal class token
-            for blk in self.transformer.resblocks:
+        self.share_adapter, self.bottleneck, self.linear_adapter = bool(share_adapter), bottleneck, bool(linear_adapter)
+        for blk in self.transformer.resblocks:
+            if not self.with_t_cls_token:   # reference :109-110: the T_Adapter exists only with the temporal class token
                 del blk.T_Adapter
+            if self.linear_adapter:         # reference :125-136: the linear adapters replace S_Adapter and MLP_Adapter
+                del blk.S_Adapter, blk.MLP_Adapter
+                for a in lin.adapter_names(self.share_adapter, False):
+                    setattr(blk, a, lin.Linear_Adapter(width, bottleneck))
         self.head_shifts = head_shifts(num_frames, heads)
         self.variant = 'zeroi2v'
-        self._adapter_names = ("MLP_Adapter", "S_Adapter") + (("T_Adapter",) if self.with_t_cls_token else ())
+        if self.linear_adapter:
+            self._adapter_names = lin.adapter_names(self.share_adapter, self.with_t_cls_token)
+        else:
+            self._adapter_names = ("MLP_Adapter", "S_Adapter") + (("T_Adapter",) if self.with_t_cls_token else ())
         self._fp8_warned = False
+        self._merged, self._merge_cache = False, None
+
+    def init_weights(self, pretrained=None):
+        """ViT_CLIP's policy, with the reference's quirks in the linear mode (:397-458): ``Linear_Adapter.init_weights`` is
+        never called, every nn.Linear gets trunc_normal_(.02), and the zeroing loops match ``MLP_Adapter_in / _out.D_fc2`` (and
+        ``T_Adapter``) by name but not ``Attn_Adapter_*``, whose D_fc2 therefore starts non-zero.  With that and the doubled
+        skip of the MLP adapters, an untrained linear model is NOT the frozen CLIP model."""
+        super().init_weights(pretrained)
+        if self.linear_adapter:
+            for blk in self.transformer.resblocks:
+                for a in ("MLP_Adapter_in", "MLP_Adapter_out"):
+                    nn.init.constant_(getattr(blk, a).D_fc2.weight, 0)
+                    nn.init.constant_(getattr(blk, a).D_fc2.bias, 0)
+
+    def _frozen_block(self, blk):
+        return lin._FrozenLin(blk, self._adapter_names) if self.linear_adapter else super()._frozen_block(blk)
+
+    # ---- merging (linear mode): the adapters folded into the frozen weights --------------------------------------------
+    @property
+    def merged(self) -> bool:
+        return self._merged
+
+    def merge_adapters(self):
+        """Fold every linear adapter into the frozen weight beside it (``zeroi2v_linear.fold_block``) and stage the result as
+        a second set of frozen operands: from now on a no-grad forward runs every block without any adapter work, and a
+        forward that needs gradients raises.  The fold is redone when an adapter (or frozen) tensor has changed."""
+        if not self.linear_adapter:
+            raise RuntimeError("ViT_CLIP_ZEROI2V.merge_adapters(): only the linear adapters (linear_adapter=True) fold into "
+                               "the frozen weights")
+        self._merged = True
+        self._merged_operands()
+        return self
+
+    def unmerge_adapters(self):
+        self._merged, self._merge_cache = False, None
+        return self
+
+    def _merged_operands(self):
+        """per-block merged operands; rebuilt only when a block's tensor changed or moved"""
+        # (FlatAdamW updates the adapters through raw pointers -- no tensor version changes -- and bumps `weights_epoch`)
+        key = tuple((p.data_ptr(), p._version) for p in self._param_slots(self.transformer, "blocks")) + (self.weights_epoch,)
+        if self._merge_cache is None or self._merge_cache[0] != key:
+            with torch.no_grad():
+                self._merge_cache = (key, [lin.fold_block(b, self.share_adapter, self.with_t_cls_token)
+                                           for b in self.transformer.resblocks])
+        return self._merge_cache[1]
 
     def set_precision(self, precision: str):
         if precision == 'fp32':
@@ -297,6 +381,9 @@ class ViT_CLIP_ZEROI2V(ViT_CLIP):
         return m[:, :P].contiguous(), m[:, P:].contiguous()
 
     def forward(self, x: torch.Tensor):
+        if self._merged and torch.is_grad_enabled() and any(p.requires_grad for p in self._trainable_list()):
+            raise RuntimeError("ViT_CLIP_ZEROI2V: the adapters are merged into the frozen weights, which has no backward; call "
+                               "unmerge_adapters() before a forward that needs gradients")
         blend = self._take_blend_check_clip(x, "ViT_CLIP_ZEROI2V")
         N = (x.shape[3] // self.patch_size) ** 2 + 1
         if N + int(self.with_t_cls_token) > 288:

@@ -32,7 +32,7 @@ extern "C" {
 
 typedef uint16_t aim_bf16;
 
-#define AIM_ABI_VERSION 15
+#define AIM_ABI_VERSION 16
 
 int aim_version(void);                /* == AIM_ABI_VERSION */
 const char* aim_last_error(void);     /* message of the last failing call on this thread */
@@ -357,6 +357,43 @@ int aim_tattn_fwd_infer(const aim_bf16* qkv, aim_bf16* out, uint8_t* out_fp8, in
 int aim_add_bf16(const aim_bf16* a, int64_t lda, const aim_bf16* b, int64_t ldb, aim_bf16* out, int64_t ldo, int R, int C,
                  void* stream);
 int aim_acc_bf16(float* x, const aim_bf16* s, int64_t lds, int R, int C, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Fused low-rank linear adapters (ABI 16) -- ZeroI2V's Linear_Adapter, vit_clip_zeroI2V.py:15-38: LA(x) = x + D_fc2(D_fc1(x)),
+ * no activation, r hidden units.  Two chained MFMA products per adapter; the r-wide intermediate goes from the first to the
+ * second through LDS and is also stored, rounded to bf16, because the other direction needs it.  G in {1, 3} adapters share
+ * one input (forward) or one input gradient (backward).  Every weight is K-contiguous, dense:
+ *   aim_lowrank_fwd   H_g  = bf16(X W1_g^T + b1_g)        wa[g] = W1_g   [r, D]   ba[g] = b1_g [r] f32 (NULL: none)
+ *                     Y_g  = alpha X + H_g W2_g^T + b2_g  wb[g] = W2_g   [D, r]   bb[g] = b2_g [D] f32 (NULL: none)
+ *                     x[0] = X [M, D] (ldx) ; h[g] = H_g [M, r] (ldh; NULL: not stored) ; y[g] = Y_g [M, D] bf16 (ldy).
+ *                     G == 1 only: y32 [M, D] f32 (ld32) = resid (ldr) + Y_0 before its rounding; y[0] may then be NULL.
+ *   aim_lowrank_bwd   dH_g = bf16(dY_g W2_g)              wa[g] = W2_g^T [r, D]
+ *                     dX   = bf16(alpha sum_g dY_g + sum_g dH_g W1_g)      wb[g] = W1_g^T [D, r]
+ *                     x[g] = dY_g [M, D] (one ldx) ; h[g] = dH_g [M, r] (ldh, required) ; y[0] = dX [M, D] (ldy).
+ * The second product reads the ROUNDED intermediate.  alpha is 1 or 2.  No atomics and one summation order: equal bits on
+ * every run.  Requirements: M >= 1; D a multiple of 64, at most 8192; r a multiple of 8, at most 256; ldx a multiple of 8,
+ * ldh / ldy / ld32 / ldr multiples of 4; x and the weights 16-byte aligned, h and y 8-byte, biases / y32 / resid 16-byte.
+ * Anything else is refused before any launch.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct aim_lowrank_args {
+    const aim_bf16* x[3];
+    int32_t ldx;
+    const aim_bf16* wa[3];
+    const float* ba[3];
+    aim_bf16* h[3];
+    int32_t ldh;
+    const aim_bf16* wb[3];
+    const float* bb[3];
+    aim_bf16* y[3];
+    int32_t ldy;
+    float* y32;
+    const float* resid;
+    int32_t ld32, ldr;
+    int32_t M, D, r, G;
+    float alpha;
+} aim_lowrank_args;
+int aim_lowrank_fwd(const aim_lowrank_args* a, void* stream);
+int aim_lowrank_bwd(const aim_lowrank_args* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * lamda = cw / (cw + ow) per frame -- vit_clip.py:149-151, 184-186, 272.
