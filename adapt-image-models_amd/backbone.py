@@ -844,10 +844,8 @@ def _embed_forward(model, frozen, imgs, temporal):
     Kp = frozen["conv"].shape[1]
     A = _empty((BT * G * G, Kp), BF16, dev)
     blend, model._blend_now = model._blend_now, None
-    if blend is not None:    # Mixup / Cutmix applied while gathering: the blended clip batch is never written
-        ops.patchify_blend(imgs, A, B, T, Hh, Ww, p, Kp, *model._norm_now, blend=blend)
-    else:
-        ops.patchify(imgs, A, B, T, Hh, Ww, p, Kp, *model._norm_now)
+    # a Mixup / Cutmix is applied while gathering: the blended clip batch is never written
+    ops.patchify(imgs, A, B, T, Hh, Ww, p, Kp, *model._norm_now, blend=blend)
     tok = _empty((BT * G * G, D), BF16, dev)
     ops.gemm(A, frozen["conv"], ops.EPI_BF16, tok)
     del A

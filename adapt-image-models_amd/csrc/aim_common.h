@@ -52,28 +52,18 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
-// ---- mini-batch blending fused into the patch gather (aim_patchify_blend / aim_patchify_blend_f32) ----------------------
-// Clip b of the batch pairs with clip partner[b].  mode 1 (mixup): lam * v(b) + oml * v(partner[b]); mode 2 (cutmix):
-// v(partner[b]) for pixels in rows [y1, y2) x columns [x1, x2) of every frame and channel, v(b) elsewhere.
-struct AimBlend {
-    const int* partner;
-    int mode;
-    float lam, oml;
-    int x1, y1, x2, y2;
-};
-// the reference's eager `lam * a + (1 - lam) * b` rounds each product and the sum: no contraction into an FMA here
-__device__ __forceinline__ float blend_mix(float a, float b, float lam, float oml) {
-    return __fadd_rn(__fmul_rn(lam, a), __fmul_rn(oml, b));
-}
-// the partner of clip b: the host builds a permutation, the clamp keeps a bad table from reading outside the batch
-__device__ __forceinline__ long long blend_partner(const AimBlend& bl, long long b, int B) {
-    return (long long)min(max(bl.partner[b], 0), B - 1);
-}
-__device__ __forceinline__ bool blend_in_box(const AimBlend& bl, int y, int x) {
-    return y >= bl.y1 && y < bl.y2 && x >= bl.x1 && x < bl.x2;
-}
-
 __device__ __forceinline__ float bf2f(bf16_t v) { return (float)v; }
+
+// four consecutive row elements, fp32 or bf16, as f32x4
+template <typename T>
+__device__ __forceinline__ f32x4 load4f(const T* p) {
+    if constexpr (sizeof(T) == 4) {
+        return *(const f32x4*)p;
+    } else {
+        const bf16x4 b = *(const bf16x4*)p;
+        return f32x4{(float)b[0], (float)b[1], (float)b[2], (float)b[3]};
+    }
+}
 
 __device__ __forceinline__ bf16x4 pack4(float a, float b, float c, float d) {
     bf16x4 r;

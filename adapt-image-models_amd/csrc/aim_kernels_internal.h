@@ -26,8 +26,21 @@ int aim_gemm_small_launch(const GemmArgs& g, int epi, int batch, hipStream_t st)
 int aim_gemm_small_fp8_launch(const GemmArgs& g, int epi, hipStream_t st);
 // rows of a thin last tile round that go to the small-tile kernel (0: no peel); fills M0 = rows of the whole rounds
 int aim_gemm_peel_rows(const GemmArgs& g, int* M0);
-// argument checks of the fused-blend patch gathers (embed_misc.hip); nonzero: the error is set
-int aim_blend_check(const char* who, const int* partner, int mode, int H, int W, int x1, int y1, int x2, int y2);
+// Mini-batch blending fused into the patch gather.  Clip b of the batch pairs with clip partner[b].  mode 1 (mixup):
+// lam * v(b) + oml * v(partner[b]); mode 2 (cutmix): v(partner[b]) for pixels in rows [y1, y2) x columns [x1, x2) of every
+// frame and channel, v(b) elsewhere.
+struct AimBlend {
+    const int* partner;
+    int mode;
+    float lam, oml;
+    int x1, y1, x2, y2;
+};
+// The launcher of the one patch-gather kernel (embed_misc.hip) behind the four aim_patchify* entry points, which keep their
+// own shape and pointer checks and their own in_dtype refusal.  blend: null for a plain gather, else checked here; who: the
+// prefix of the entry point's messages ("patchify_f32").  0: launched; -1, no error set: no gather for this in_dtype, which
+// the entry point refuses in its own words; other nonzero: the error is set.  A must be 16-byte aligned.
+int aim_patchify_launch(const char* who, bool f32_out, const void* imgs, int in_dtype, const float* mean3, const float* std3,
+                        void* A, int B, int T, int H, int W, int p, int Kp, const AimBlend* blend, hipStream_t st);
 // EXPSUM problems of one 256x256 tile per batch item run on the persistent kernel (8 partial slots per item)
 static inline bool aim_expsum_use256(int M, int N) {
     static const bool on = [] { const char* e = getenv("AIM_EXPSUM_256"); return !e || atoi(e) != 0; }();

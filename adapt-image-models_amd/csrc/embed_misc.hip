@@ -5,6 +5,10 @@
 //   class_embedding concat (:439), + positional_embedding (:440), + temporal_embedding (:443-445),
 //   ln_pre (:447).  Optional uint8 input fuses the GPUNormalize pre-hook
 //   (mmaction/utils/module_hooks.py:73-85): x.float().sub_(mean).div_(std).
+//   The patch gather is ONE kernel template, patchify_kernel<TIN, TOUT, BLEND>: bf16 or f32 output (the fp32 verification
+//   mode's entry points sit in fp32.hip), with or without a mixup / cutmix of two clips.  Its four entry points
+//   (aim_patchify, aim_patchify_blend, aim_patchify_f32, aim_patchify_blend_f32) keep their own checks and share
+//   aim_patchify_launch.
 // frame_sum / colsum / cast / scale_rows: bandwidth-bound helpers for the hand-written backward
 //   (per-frame token sums for the broadcast S_Adapter term, bias gradients, bf16 weight staging).
 #include "aim_common.h"
@@ -14,75 +18,30 @@ namespace {
 
 constexpr int MAXC = 8;
 
-// A[(bt*G*G + gy*G + gx)][c*p*p + py*p + px] = img[b][c][t][gy*p+py][gx*p+px]; one thread per 8 columns
-template <typename TIN>
-__global__ __launch_bounds__(256) void patchify_kernel(const TIN* __restrict__ img, const float* __restrict__ mean3,
-                                                       const float* __restrict__ std3, bf16_t* __restrict__ A, int B,
-                                                       int T, int H, int W, int p, int Kp) {
-    const int G = W / p, Gy = H / p, K = 3 * p * p;
-    const long long rows = (long long)B * T * Gy * G;
-    const int cpr = Kp / 8;
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= rows * cpr) return;
-    const long long row = idx / cpr;
-    const int k0 = (int)(idx - row * cpr) * 8;
-    const int gx = (int)(row % G), gy = (int)((row / G) % Gy);
-    const long long bt = row / ((long long)G * Gy);
-    const int t = (int)(bt % T);
-    const long long b = bt / T;
-    bf16x8 o;
-    if ((p & 7) == 0 && (W & 7) == 0 && k0 + 8 <= K && ((unsigned long long)img & 15) == 0) {
-        // patch width a multiple of 8 (ViT-B/16): the thread's 8 columns are 8 consecutive pixels of one image row -> one or
-        // two 16-byte loads instead of eight scalar ones with their index arithmetic
-        const int c = k0 / (p * p), rem = k0 - c * p * p, py = rem / p, px = rem - py * p;
-        const TIN* src = img + (((b * 3 + c) * T + t) * H + (gy * p + py)) * (long long)W + gx * p + px;
-        float v[8];
-        if constexpr (sizeof(TIN) == 4) {
-            const f32x4 a0 = *(const f32x4*)src, a1 = *(const f32x4*)(src + 4);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                v[e] = a0[e];
-                v[4 + e] = a1[e];
-            }
-        } else if constexpr (sizeof(TIN) == 2) {
-            const bf16x8 a0 = *(const bf16x8*)src;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = (float)a0[e];
-        } else {
-            const uint2 a0 = *(const uint2*)src;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                v[e] = (float)((a0.x >> (8 * e)) & 0xffu);
-                v[4 + e] = (float)((a0.y >> (8 * e)) & 0xffu);
-            }
-        }
-        if (mean3) {
-            const float m = mean3[c], sd = std3[c];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = (v[e] - m) / sd;
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = (bf16_t)v[e];
-    } else {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const int k = k0 + e;
-            float v = 0.f;
-            if (k < K) {
-                const int c = k / (p * p), rem = k - c * p * p, py = rem / p, px = rem - py * p;
-                const long long src = (((b * 3 + c) * T + t) * H + (gy * p + py)) * (long long)W + gx * p + px;
-                v = (float)img[src];
-                if (mean3) v = (v - mean3[c]) / std3[c];
-            }
-            o[e] = (bf16_t)v;
-        }
-    }
-    *(bf16x8*)(A + row * Kp + k0) = o;
+// ---- the patch gather, with mini-batch blending fused into it (AimBlend: aim_kernels_internal.h) --------------------------
+// the reference's eager `lam * a + (1 - lam) * b` rounds each product and the sum: no contraction into an FMA here
+__device__ __forceinline__ float blend_mix(float a, float b, float lam, float oml) {
+    return __fadd_rn(__fmul_rn(lam, a), __fmul_rn(oml, b));
+}
+// the partner of clip b: the host builds a permutation, the clamp keeps a bad table from reading outside the batch
+__device__ __forceinline__ long long blend_partner(const AimBlend& bl, long long b, int B) {
+    return (long long)min(max(bl.partner[b], 0), B - 1);
+}
+__device__ __forceinline__ bool blend_in_box(const AimBlend& bl, int y, int x) {
+    return y >= bl.y1 && y < bl.y2 && x >= bl.x1 && x < bl.x2;
 }
 
-// 8 consecutive pixels of one image row (16-byte aligned) -> f32
+// one pixel, normalised when the uint8 GPUNormalize is fused
 template <typename TIN>
-__device__ __forceinline__ void load_px8(const TIN* src, float v[8]) {
+__device__ __forceinline__ float load_px(const TIN* src, const float* mean3, const float* std3, int c) {
+    float v = (float)*src;
+    if (mean3) v = (v - mean3[c]) / std3[c];
+    return v;
+}
+// 8 consecutive pixels of one image row (16-byte aligned image, x a multiple of 8): one or two 16-byte loads instead of eight
+// scalar ones with their index arithmetic
+template <typename TIN>
+__device__ __forceinline__ void load_px8(const TIN* src, const float* mean3, const float* std3, int c, float v[8]) {
     if constexpr (sizeof(TIN) == 4) {
         const f32x4 a0 = *(const f32x4*)src, a1 = *(const f32x4*)(src + 4);
 #pragma unroll
@@ -90,6 +49,10 @@ __device__ __forceinline__ void load_px8(const TIN* src, float v[8]) {
             v[e] = a0[e];
             v[4 + e] = a1[e];
         }
+    } else if constexpr (sizeof(TIN) == 2) {
+        const bf16x8 a0 = *(const bf16x8*)src;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = (float)a0[e];
     } else {
         const uint2 a0 = *(const uint2*)src;
 #pragma unroll
@@ -98,88 +61,95 @@ __device__ __forceinline__ void load_px8(const TIN* src, float v[8]) {
             v[4 + e] = (float)((a0.y >> (8 * e)) & 0xffu);
         }
     }
+    if (mean3) {
+        const float m = mean3[c], sd = std3[c];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = (v[e] - m) / sd;
+    }
 }
 
-// patchify_kernel with a mixup / cutmix of two clips applied while gathering (AimBlend): the blended clip is never
-// written.  Mixup blends the NORMALISED values when the uint8 GPUNormalize is fused (lam * norm(a) + oml * norm(b)).
-template <typename TIN>
-__global__ __launch_bounds__(256) void patchify_blend_kernel(const TIN* __restrict__ img, const float* __restrict__ mean3,
-                                                             const float* __restrict__ std3, bf16_t* __restrict__ A, int B,
-                                                             int T, int H, int W, int p, int Kp, AimBlend bl) {
+// A[(bt*G*G + gy*G + gx)][c*p*p + py*p + px] = img[b][c][t][gy*p+py][gx*p+px], bf16 or f32; one thread per 16 bytes of a row
+// of A (pad columns k >= 3 p p: zero).  BLEND: a mixup / cutmix of clip b and clip partner[b] is applied while gathering, so
+// the blended clip is never written; mixup blends the NORMALISED values (lam * norm(a) + oml * norm(b)).  `bl` is read by
+// the BLEND instantiations only.
+template <typename TIN, typename TOUT, bool BLEND>
+__global__ __launch_bounds__(256) void patchify_kernel(const TIN* __restrict__ img, const float* __restrict__ mean3,
+                                                       const float* __restrict__ std3, TOUT* __restrict__ A, int B, int T,
+                                                       int H, int W, int p, int Kp, AimBlend bl) {
+    constexpr int NC = 16 / sizeof(TOUT);
     const int G = W / p, Gy = H / p, K = 3 * p * p;
     const long long rows = (long long)B * T * Gy * G;
-    const int cpr = Kp / 8;
+    const int cpr = Kp / NC;
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= rows * cpr) return;
     const long long row = idx / cpr;
-    const int k0 = (int)(idx - row * cpr) * 8;
+    const int k0 = (int)(idx - row * cpr) * NC;
     const int gx = (int)(row % G), gy = (int)((row / G) % Gy);
     const long long bt = row / ((long long)G * Gy);
     const int t = (int)(bt % T);
-    const long long b = bt / T, pb = blend_partner(bl, b, B);
-    const bool mixup = bl.mode == 1;
-    bf16x8 o;
-    if ((p & 7) == 0 && (W & 7) == 0 && k0 + 8 <= K && ((unsigned long long)img & 15) == 0) {
-        // 8 consecutive pixels of one image row, as in patchify_kernel.  Cutmix loads the partner's run only where the box
-        // covers it: a run outside the box reads clip b, a run inside it clip partner[b], a run across an edge both.
+    const long long b = bt / T, plane = (long long)T * H * W;
+    long long pb = b;
+    bool mixup = false;
+    if constexpr (BLEND) {
+        pb = blend_partner(bl, b, B);
+        mixup = bl.mode == 1;
+    }
+    float v[8];      // the first NC are the thread's columns; f32 output (a verification mode) always gathers pixel by pixel
+    if (NC == 8 && (p & 7) == 0 && (W & 7) == 0 && k0 + 8 <= K && ((unsigned long long)img & 15) == 0) {
+        // patch width a multiple of 8 (ViT-B/16), bf16 output: the thread's 8 columns are 8 consecutive pixels of one image row
         const int c = k0 / (p * p), rem = k0 - c * p * p, py = rem / p, px = rem - py * p;
         const int y = gy * p + py, x0 = gx * p + px;
         const long long pix = ((long long)t * H + y) * W + x0;
-        const TIN* sa = img + (b * 3 + c) * (long long)T * H * W + pix;
-        const TIN* sb = img + (pb * 3 + c) * (long long)T * H * W + pix;
-        const bool rowin = y >= bl.y1 && y < bl.y2;
-        const bool none = !mixup && (!rowin || x0 + 8 <= bl.x1 || x0 >= bl.x2);
-        const bool all = !mixup && rowin && x0 >= bl.x1 && x0 + 8 <= bl.x2;
-        float va[8] = {}, vb[8] = {};
-        if (!all) load_px8(sa, va);
-        if (!none) load_px8(sb, vb);
-        if (mean3) {
-            const float m = mean3[c], sd = std3[c];
+        const TIN* sa = img + (b * 3 + c) * plane + pix;
+        if constexpr (BLEND) {
+            // cutmix loads the partner's run only where the box covers it: a run outside the box reads clip b, a run inside
+            // it clip partner[b], a run across an edge both
+            const TIN* sb = img + (pb * 3 + c) * plane + pix;
+            const bool rowin = y >= bl.y1 && y < bl.y2;
+            const bool none = !mixup && (!rowin || x0 + 8 <= bl.x1 || x0 >= bl.x2);
+            const bool all = !mixup && rowin && x0 >= bl.x1 && x0 + 8 <= bl.x2;
+            load_px8(all ? sb : sa, mean3, std3, c, v);
+            if (!none && !all) {
+                float q[8];
+                load_px8(sb, mean3, std3, c, q);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                va[e] = (va[e] - m) / sd;
-                vb[e] = (vb[e] - m) / sd;
+                for (int e = 0; e < 8; ++e) {
+                    if (mixup)
+                        v[e] = blend_mix(v[e], q[e], bl.lam, bl.oml);
+                    else if (x0 + e >= bl.x1 && x0 + e < bl.x2)
+                        v[e] = q[e];
+                }
             }
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            float v;
-            if (mixup)
-                v = blend_mix(va[e], vb[e], bl.lam, bl.oml);
-            else if (none)
-                v = va[e];
-            else if (all)
-                v = vb[e];
-            else
-                v = (x0 + e >= bl.x1 && x0 + e < bl.x2) ? vb[e] : va[e];
-            o[e] = (bf16_t)v;
+        } else {
+            load_px8(sa, mean3, std3, c, v);
         }
     } else {
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
+        for (int e = 0; e < NC; ++e) {
             const int k = k0 + e;
-            float v = 0.f;
+            v[e] = 0.f;
             if (k < K) {
                 const int c = k / (p * p), rem = k - c * p * p, py = rem / p, px = rem - py * p;
                 const int y = gy * p + py, x = gx * p + px;
                 const long long pix = ((long long)t * H + y) * W + x;
-                const long long sa = (b * 3 + c) * (long long)T * H * W + pix, sb = (pb * 3 + c) * (long long)T * H * W + pix;
-                if (mixup) {
-                    float a = (float)img[sa], q = (float)img[sb];
-                    if (mean3) {
-                        a = (a - mean3[c]) / std3[c];
-                        q = (q - mean3[c]) / std3[c];
-                    }
-                    v = blend_mix(a, q, bl.lam, bl.oml);
+                const TIN* sa = img + (b * 3 + c) * plane + pix;
+                if constexpr (BLEND) {
+                    const TIN* sb = img + (pb * 3 + c) * plane + pix;
+                    if (mixup)
+                        v[e] = blend_mix(load_px(sa, mean3, std3, c), load_px(sb, mean3, std3, c), bl.lam, bl.oml);
+                    else
+                        v[e] = load_px(blend_in_box(bl, y, x) ? sb : sa, mean3, std3, c);
                 } else {
-                    v = (float)img[blend_in_box(bl, y, x) ? sb : sa];
-                    if (mean3) v = (v - mean3[c]) / std3[c];
+                    v[e] = load_px(sa, mean3, std3, c);
                 }
             }
-            o[e] = (bf16_t)v;
         }
     }
-    *(bf16x8*)(A + row * Kp + k0) = o;
+    typedef __attribute__((ext_vector_type(NC))) TOUT out_t;
+    out_t o;
+#pragma unroll
+    for (int e = 0; e < NC; ++e) o[e] = (TOUT)v[e];
+    *(out_t*)(A + row * Kp + k0) = o;
 }
 
 __device__ __forceinline__ f32x4 embed_value(const bf16_t* tok, const float* cls, const float* pos, const float* tmp,
@@ -250,16 +220,6 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const bf16_t* __restrict_
 
 // grid (T, chunks): every wave walks rows (b, n) of frame-time t, accumulates ln_pre's input gradient
 // in registers and adds it into dtemporal[t] once at the end.
-template <typename T>
-__device__ __forceinline__ f32x4 load4f(const T* p) {
-    if constexpr (sizeof(T) == 4) {
-        return *(const f32x4*)p;
-    } else {
-        const bf16x4 b = *(const bf16x4*)p;
-        return f32x4{(float)b[0], (float)b[1], (float)b[2], (float)b[3]};
-    }
-}
-
 template <int NC, typename TDX>
 __global__ __launch_bounds__(256) void embed_bwd_kernel(const TDX* __restrict__ dx, const bf16_t* __restrict__ tok,
                                                         const float* __restrict__ cls, const float* __restrict__ pos,
@@ -649,26 +609,57 @@ extern "C" int aim_adamw_flat(float* p, const float* g, float* m, float* v, int6
     return 0;
 }
 
+// BLENDABLE = false: bf16 clips, which no blend entry point accepts (no BLEND instantiation for them)
+template <typename TIN, typename TOUT, bool BLENDABLE = true>
+static void patchify_launch(dim3 grid, hipStream_t st, const void* imgs, const float* mean3, const float* std3, void* A, int B,
+                            int T, int H, int W, int p, int Kp, const AimBlend* blend) {
+    if constexpr (BLENDABLE) {
+        if (blend) {
+            hipLaunchKernelGGL((patchify_kernel<TIN, TOUT, true>), grid, dim3(256), 0, st, (const TIN*)imgs, mean3, std3, (TOUT*)A,
+                               B, T, H, W, p, Kp, *blend);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((patchify_kernel<TIN, TOUT, false>), grid, dim3(256), 0, st, (const TIN*)imgs, mean3, std3, (TOUT*)A, B, T,
+                       H, W, p, Kp, AimBlend{});
+}
+
+// The one launcher behind aim_patchify, aim_patchify_blend and (fp32.hip) aim_patchify_f32, aim_patchify_blend_f32, which have
+// checked the shape and the pointers.  who: the prefix of the entry point's messages.  Returns -1, with no error set, when
+// there is no gather for in_dtype with this output type and blend: the entry point words that refusal itself.
+int aim_patchify_launch(const char* who, bool f32_out, const void* imgs, int in_dtype, const float* mean3, const float* std3,
+                        void* A, int B, int T, int H, int W, int p, int Kp, const AimBlend* blend, hipStream_t st) {
+    if (blend) {
+        AIM_CHECK_ARG(blend->partner, "%s: partner is NULL", who);
+        AIM_CHECK_ARG(blend->mode == 1 || blend->mode == 2, "%s: mode must be 1 (mixup) or 2 (cutmix), got %d", who, blend->mode);
+        AIM_CHECK_ARG(blend->mode == 1 || (0 <= blend->x1 && blend->x1 <= blend->x2 && blend->x2 <= W && 0 <= blend->y1 &&
+                                           blend->y1 <= blend->y2 && blend->y2 <= H),
+                      "%s: box x [%d, %d) y [%d, %d) outside the %d x %d image", who, blend->x1, blend->x2, blend->y1, blend->y2, W, H);
+    }
+    decltype(&patchify_launch<float, float>) launch = nullptr;
+    if (in_dtype == 0)
+        launch = f32_out ? patchify_launch<float, float> : patchify_launch<float, bf16_t>;
+    else if (in_dtype == 1)
+        launch = f32_out ? patchify_launch<uint8_t, float> : patchify_launch<uint8_t, bf16_t>;
+    else if (in_dtype == 2 && !f32_out && !blend)
+        launch = patchify_launch<bf16_t, bf16_t, false>;
+    if (!launch) return -1;
+    const long long total = (long long)B * T * (H / p) * (W / p) * (Kp / (f32_out ? 4 : 8));      // a thread per 16 bytes of A
+    launch(dim3((unsigned)((total + 255) / 256)), st, imgs, mean3, std3, A, B, T, H, W, p, Kp, blend);
+    char name[40];
+    snprintf(name, sizeof name, "aim_%s", who);
+    AIM_CHECK_LAUNCH(name);
+    return 0;
+}
+
 extern "C" int aim_patchify(const void* imgs, int in_dtype, const float* mean3, const float* std3, aim_bf16* A, int B,
                             int T, int H, int W, int p, int Kp, void* stream) {
     AIM_CHECK_ARG(B > 0 && T > 0 && p > 0 && H % p == 0 && W % p == 0, "patchify: bad shape H=%d W=%d p=%d", H, W, p);
     AIM_CHECK_ARG(Kp >= 3 * p * p && (Kp % 8) == 0, "patchify: Kp=%d must be >= 3*p*p and a multiple of 8", Kp);
     AIM_CHECK_ARG(imgs && A && ((!mean3) == (!std3)), "patchify: null pointer");
-    const long long total = (long long)B * T * (H / p) * (W / p) * (Kp / 8);
-    const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-    hipStream_t st = (hipStream_t)stream;
-    if (in_dtype == 0)
-        hipLaunchKernelGGL(patchify_kernel<float>, grid, block, 0, st, (const float*)imgs, mean3, std3, (bf16_t*)A, B, T, H, W, p, Kp);
-    else if (in_dtype == 1)
-        hipLaunchKernelGGL(patchify_kernel<uint8_t>, grid, block, 0, st, (const uint8_t*)imgs, mean3, std3, (bf16_t*)A, B, T, H, W, p, Kp);
-    else if (in_dtype == 2)
-        hipLaunchKernelGGL(patchify_kernel<bf16_t>, grid, block, 0, st, (const bf16_t*)imgs, mean3, std3, (bf16_t*)A, B, T, H, W, p, Kp);
-    else {
-        aim_set_error("patchify: in_dtype must be 0 (f32), 1 (uint8) or 2 (bf16), got %d", in_dtype);
-        return 1;
-    }
-    AIM_CHECK_LAUNCH("aim_patchify");
-    return 0;
+    const int rc = aim_patchify_launch("patchify", false, imgs, in_dtype, mean3, std3, A, B, T, H, W, p, Kp, nullptr, (hipStream_t)stream);
+    AIM_CHECK_ARG(rc >= 0, "patchify: in_dtype must be 0 (f32), 1 (uint8) or 2 (bf16), got %d", in_dtype);
+    return rc;
 }
 
 extern "C" int aim_embed_ln(const aim_bf16* tok, const float* cls, const float* pos, const float* temporal,
@@ -825,36 +816,14 @@ extern "C" int aim_scale_rows(const float* x, const float* s, aim_bf16* y, float
     return 0;
 }
 
-// shared by aim_patchify_blend and aim_patchify_blend_f32 (fp32.hip)
-int aim_blend_check(const char* who, const int* partner, int mode, int H, int W, int x1, int y1, int x2, int y2) {
-    AIM_CHECK_ARG(partner, "%s: partner is NULL", who);
-    AIM_CHECK_ARG(mode == 1 || mode == 2, "%s: mode must be 1 (mixup) or 2 (cutmix), got %d", who, mode);
-    AIM_CHECK_ARG(mode == 1 || (0 <= x1 && x1 <= x2 && x2 <= W && 0 <= y1 && y1 <= y2 && y2 <= H),
-                  "%s: box x [%d, %d) y [%d, %d) outside the %d x %d image", who, x1, x2, y1, y2, W, H);
-    return 0;
-}
-
 extern "C" int aim_patchify_blend(const void* imgs, int in_dtype, const float* mean3, const float* std3, aim_bf16* A, int B,
                                   int T, int H, int W, int p, int Kp, const int* partner, int mode, float lam, float oml,
                                   int x1, int y1, int x2, int y2, void* stream) {
     AIM_CHECK_ARG(B > 0 && T > 0 && p > 0 && H % p == 0 && W % p == 0, "patchify_blend: bad shape H=%d W=%d p=%d", H, W, p);
     AIM_CHECK_ARG(Kp >= 3 * p * p && (Kp % 8) == 0, "patchify_blend: Kp=%d must be >= 3*p*p and a multiple of 8", Kp);
     AIM_CHECK_ARG(imgs && A && ((!mean3) == (!std3)), "patchify_blend: null pointer");
-    if (aim_blend_check("patchify_blend", partner, mode, H, W, x1, y1, x2, y2)) return 1;
     const AimBlend bl{partner, mode, lam, oml, x1, y1, x2, y2};
-    const long long total = (long long)B * T * (H / p) * (W / p) * (Kp / 8);
-    const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-    hipStream_t st = (hipStream_t)stream;
-    if (in_dtype == 0)
-        hipLaunchKernelGGL(patchify_blend_kernel<float>, grid, block, 0, st, (const float*)imgs, mean3, std3, (bf16_t*)A, B, T, H,
-                           W, p, Kp, bl);
-    else if (in_dtype == 1)
-        hipLaunchKernelGGL(patchify_blend_kernel<uint8_t>, grid, block, 0, st, (const uint8_t*)imgs, mean3, std3, (bf16_t*)A, B, T,
-                           H, W, p, Kp, bl);
-    else {
-        aim_set_error("patchify_blend: in_dtype must be 0 (f32) or 1 (uint8), got %d", in_dtype);
-        return 1;
-    }
-    AIM_CHECK_LAUNCH("aim_patchify_blend");
-    return 0;
+    const int rc = aim_patchify_launch("patchify_blend", false, imgs, in_dtype, mean3, std3, A, B, T, H, W, p, Kp, &bl, (hipStream_t)stream);
+    AIM_CHECK_ARG(rc >= 0, "patchify_blend: in_dtype must be 0 (f32) or 1 (uint8), got %d", in_dtype);
+    return rc;
 }

@@ -12,17 +12,7 @@ namespace {
 
 constexpr int MAXC = 8;  // float4 chunks per lane: D <= 8*4*64 = 2048 (template NC = chunks actually used)
 
-// (row elements as f32x4 from an fp32 or a bf16 row: the fp8 inference path keeps its residual stream in bf16)
-template <typename TX>
-__device__ __forceinline__ f32x4 ln_load4(const TX* p) {
-    if constexpr (sizeof(TX) == 4) {
-        return *(const f32x4*)p;
-    } else {
-        const bf16x4 b = *(const bf16x4*)p;
-        return f32x4{(float)b[0], (float)b[1], (float)b[2], (float)b[3]};
-    }
-}
-
+// (TX: an fp32 or a bf16 row, read through load4f: the fp8 inference path keeps its residual stream in bf16)
 template <int NC, typename TX = float>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const TX* __restrict__ x, long long ldx,
                                                      const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -40,7 +30,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const TX* __restrict__ x, l
     for (int c = 0; c < NC; ++c) {
         const int ch = lane + c * 64;
         if (ch < nch) {
-            v[c] = ln_load4(xr + ch * 4);
+            v[c] = load4f(xr + ch * 4);
             s += (v[c][0] + v[c][1]) + (v[c][2] + v[c][3]);
         }
     }

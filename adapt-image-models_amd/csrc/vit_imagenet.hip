@@ -13,16 +13,6 @@
 
 namespace {
 
-template <typename T>
-__device__ __forceinline__ f32x4 ld4(const T* p) {
-    if constexpr (sizeof(T) == 4) {
-        return *(const f32x4*)p;
-    } else {
-        const bf16x4 v = *(const bf16x4*)p;
-        return f32x4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
-    }
-}
-
 // x[(bt*N + n)][d] = ((n == 0 ? cls[d] : tok[bt*(N-1) + n-1][d]) + pos[n][d]) + temporal[t][d]; one thread per 4 columns
 __global__ __launch_bounds__(256) void embed_nopre_fwd_kernel(const float* __restrict__ tok, const float* __restrict__ cls,
                                                               const float* __restrict__ pos, const float* __restrict__ temporal,
@@ -51,7 +41,7 @@ __global__ __launch_bounds__(256) void embed_nopre_frames_kernel(const T* __rest
     const T* src = dx + (long long)f * N * D + d;
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     for (int n = 0; n < N; ++n) {
-        acc += ld4(src + (long long)n * D);
+        acc += load4f(src + (long long)n * D);
         if (dtok && n > 0) {
             if constexpr (sizeof(T) == 4)
                 *(f32x4*)(dtok + ((long long)f * (N - 1) + n - 1) * D + d) = *(const f32x4*)(src + (long long)n * D);
@@ -70,7 +60,7 @@ __global__ __launch_bounds__(256) void embed_nopre_tokens_kernel(const T* __rest
     const int d = (blockIdx.y * 256 + threadIdx.x) * 4;
     if (d >= D) return;
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    for (int f = 0; f < BT; ++f) acc += ld4(dx + ((long long)f * N + n) * D + d);
+    for (int f = 0; f < BT; ++f) acc += load4f(dx + ((long long)f * N + n) * D + d);
     *(f32x4*)(psum + (long long)n * D + d) = acc;
     if (dpos) *(f32x4*)(dpos + (long long)n * D + d) += acc;
 }
@@ -116,7 +106,7 @@ __global__ __launch_bounds__(256) void ln_gb_partial_kernel(const T* __restrict_
     f32x4 ag = {0.f, 0.f, 0.f, 0.f}, ab = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll 4
     for (int m = m0; m < m1; ++m) {
-        const f32x4 g = ld4(dy + (long long)m * lddy + d);
+        const f32x4 g = load4f(dy + (long long)m * lddy + d);
         const f32x4 xv = *(const f32x4*)(x + (long long)m * ldx + d);
         const float mu = mean[m], rs = rstd[m];
 #pragma unroll

@@ -654,14 +654,28 @@ def lambda_(qkv, kx, partials, ntiles, lam, one_minus, BT, N, D, scale, ss=None)
 _IN_DTYPES = {torch.float32: 0, torch.uint8: 1, torch.bfloat16: 2}
 
 
-def patchify(imgs, A, B, T, H, W, p, Kp, mean3=None, std3=None):
-    if imgs.dtype not in _IN_DTYPES:
-        raise TypeError(f"patchify: unsupported input dtype {imgs.dtype} (float32, uint8, bfloat16)")
+def patchify(imgs, A, B, T, H, W, p, Kp, mean3=None, std3=None, blend=None):
+    """The patch matrix ``A`` (bf16, or f32 for the fp32 path) of the clips ``imgs`` (float32 or uint8; bfloat16 only into a
+    bf16 ``A`` without a blend), with the uint8 normalisation fused when ``mean3`` / ``std3`` are given.  ``blend``
+    (``blending.FusedBlend``): a mixup / cutmix of clip b and clip ``blend.partner[b]`` applied while gathering.  The kernel
+    writes ``A`` 16 bytes at a time, so ``A`` starts on a 16-byte boundary."""
+    f32_out = A.dtype == F32
+    _chk(A, F32 if f32_out else BF16, "A"); _chk(mean3, F32, "mean3"); _chk(std3, F32, "std3")
+    if A.data_ptr() % 16:
+        raise ValueError("patchify: A must be 16-byte aligned")
+    entry = "aim_patchify" + ("_blend" if blend is not None else "") + ("_f32" if f32_out else "")
+    if imgs.dtype not in _IN_DTYPES or (imgs.dtype == BF16 and entry != "aim_patchify"):
+        raise TypeError(f"patchify: unsupported input dtype {imgs.dtype} for {entry} (float32, uint8; bfloat16 only for aim_patchify)")
     if not imgs.is_cuda or not imgs.is_contiguous():
         raise ValueError("patchify: imgs must be a contiguous GPU tensor")
-    _chk(A, BF16, "A"); _chk(mean3, F32, "mean3"); _chk(std3, F32, "std3")
-    check(load_library().aim_patchify(imgs.data_ptr(), _IN_DTYPES[imgs.dtype], _p(mean3), _p(std3), A.data_ptr(),
-                                      B, T, H, W, p, Kp, _stream()), "aim_patchify")
+    args = ()
+    if blend is not None:
+        _chk(blend.partner, torch.int32, "partner")
+        if blend.partner.numel() != B or not blend.partner.is_contiguous():
+            raise ValueError(f"patchify: partner must hold one index per clip ({B}), got {tuple(blend.partner.shape)}")
+        args = (blend.partner.data_ptr(), blend.mode, blend.lam, blend.oml, *blend.box)
+    check(getattr(load_library(), entry)(imgs.data_ptr(), _IN_DTYPES[imgs.dtype], _p(mean3), _p(std3), A.data_ptr(),
+                                         B, T, H, W, p, Kp, *args, _stream()), entry)
 
 
 def embed_ln(tok, cls, pos, temporal, gamma, beta, x, mean, rstd, B, T, N, D, eps=1e-5):
@@ -900,44 +914,6 @@ def lambda_f32(scores, qkv, kx, lam, one_minus, BT, N, D, scale):
         _chk(t_, F32, n_)
     check(load_library().aim_lambda_f32(scores.data_ptr(), scores.stride(-2), qkv.data_ptr(), kx.data_ptr(), kx.stride(0),
                                         lam.data_ptr(), _p(one_minus), BT, N, D, scale, _stream()), "aim_lambda_f32")
-
-
-def _blend_args(imgs, B, blend):
-    if imgs.dtype not in (torch.float32, torch.uint8):
-        raise TypeError(f"patchify_blend: unsupported input dtype {imgs.dtype} (float32, uint8)")
-    if not imgs.is_cuda or not imgs.is_contiguous():
-        raise ValueError("patchify_blend: imgs must be a contiguous GPU tensor")
-    _chk(blend.partner, torch.int32, "partner")
-    if blend.partner.numel() != B or not blend.partner.is_contiguous():
-        raise ValueError(f"patchify_blend: partner must hold one index per clip ({B}), got {tuple(blend.partner.shape)}")
-    x1, y1, x2, y2 = blend.box
-    return (blend.partner.data_ptr(), blend.mode, blend.lam, blend.oml, x1, y1, x2, y2)
-
-
-def patchify_blend(imgs, A, B, T, H, W, p, Kp, mean3=None, std3=None, blend=None):
-    """``patchify`` with a mixup / cutmix of clip b and clip ``blend.partner[b]`` applied while gathering
-    (``blending.FusedBlend``; ``aim_patchify_blend``)."""
-    args = _blend_args(imgs, B, blend)
-    _chk(A, BF16, "A"); _chk(mean3, F32, "mean3"); _chk(std3, F32, "std3")
-    check(load_library().aim_patchify_blend(imgs.data_ptr(), _IN_DTYPES[imgs.dtype], _p(mean3), _p(std3), A.data_ptr(),
-                                            B, T, H, W, p, Kp, *args, _stream()), "aim_patchify_blend")
-
-
-def patchify_blend_f32(imgs, A, B, T, H, W, p, Kp, mean3=None, std3=None, blend=None):
-    args = _blend_args(imgs, B, blend)
-    _chk(A, F32, "A"); _chk(mean3, F32, "mean3"); _chk(std3, F32, "std3")
-    check(load_library().aim_patchify_blend_f32(imgs.data_ptr(), _IN_DTYPES[imgs.dtype], _p(mean3), _p(std3), A.data_ptr(),
-                                                B, T, H, W, p, Kp, *args, _stream()), "aim_patchify_blend_f32")
-
-
-def patchify_f32(imgs, A, B, T, H, W, p, Kp, mean3=None, std3=None):
-    if imgs.dtype not in (torch.float32, torch.uint8):
-        raise TypeError(f"patchify_f32: unsupported input dtype {imgs.dtype} (float32, uint8)")
-    if not imgs.is_cuda or not imgs.is_contiguous():
-        raise ValueError("patchify_f32: imgs must be a contiguous GPU tensor")
-    _chk(A, F32, "A"); _chk(mean3, F32, "mean3"); _chk(std3, F32, "std3")
-    check(load_library().aim_patchify_f32(imgs.data_ptr(), _IN_DTYPES[imgs.dtype], _p(mean3), _p(std3), A.data_ptr(), B, T, H, W,
-                                          p, Kp, _stream()), "aim_patchify_f32")
 
 
 def embed_ln_f32(tok, cls, pos, temporal, gamma, beta, x, B, T, N, D, eps=1e-5, pre=None, mean=None, rstd=None):

@@ -35,7 +35,7 @@ def forward_f32(model, imgs, P, wants):
     if imgs.dtype != F32:
         imgs = imgs.float().contiguous()
     A = _e((BT * G * G, K), dev)
-    ops.patchify_f32(imgs, A, B, T, Hh, Ww, p, K)
+    ops.patchify(imgs, A, B, T, Hh, Ww, p, K)
     tok = _e((BT * G * G, D), dev)
     cb = P.get("patch_embed.proj.bias")
     ops.gemm_f32(A, _f(P["patch_embed.proj.weight"]).reshape(D, K), ops.EPI_BF16, tok, bias=None if cb is None else _f(cb))
@@ -106,7 +106,7 @@ class _ViTImageNetFn32(torch.autograd.Function):
             p, imgs = model.patch_size, s["imgs"]
             K = 3 * p * p
             A = _e((BT * (N - 1), K), dev)
-            ops.patchify_f32(imgs, A, B, T, imgs.shape[3], imgs.shape[4], p, K)
+            ops.patchify(imgs, A, B, T, imgs.shape[3], imgs.shape[4], p, K)
             ops.wgrad_f32(dtok, A, gconv.view(D, K))
         ctx.saved = None
         out = [None if g_ is None else (g_ if g_.dtype == p_.dtype else g_.to(p_.dtype)) for g_, p_ in zip(grads, params)]

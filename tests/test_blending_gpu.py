@@ -160,10 +160,10 @@ def test_fused_patchify_bit_identical(kind, p, H, box, dtype):
     rows = B * S * T * G2
     a_ref, a_fused = torch.empty((rows, Kp), dtype=torch.bfloat16, device=DEV), torch.empty((rows, Kp), dtype=torch.bfloat16, device=DEV)
     ops.patchify(mat, a_ref, B * S, T, H, H, p, Kp, mm3, ms3)
-    ops.patchify_blend(imgs, a_fused, B * S, T, H, H, p, Kp, m3, s3, blend=fused)
+    ops.patchify(imgs, a_fused, B * S, T, H, H, p, Kp, m3, s3, blend=fused)
     f_ref, f_fused = torch.empty((rows, K), device=DEV), torch.empty((rows, K), device=DEV)
-    ops.patchify_f32(mat, f_ref, B * S, T, H, H, p, K, mm3, ms3)
-    ops.patchify_blend_f32(imgs, f_fused, B * S, T, H, H, p, K, m3, s3, blend=fused)
+    ops.patchify(mat, f_ref, B * S, T, H, H, p, K, mm3, ms3)
+    ops.patchify(imgs, f_fused, B * S, T, H, H, p, K, m3, s3, blend=fused)
     torch.cuda.synchronize()
     assert torch.equal(a_fused.view(torch.int16), a_ref.view(torch.int16))
     assert torch.equal(f_fused.view(torch.int32), f_ref.view(torch.int32))
@@ -180,11 +180,11 @@ def test_fused_patchify_rejects_bad_arguments():
     A = torch.empty((8, 768), dtype=torch.bfloat16, device=DEV)
     part = torch.tensor([1, 0], dtype=torch.int32, device=DEV)
     with pytest.raises(RuntimeError, match="outside"):
-        ops.patchify_blend(imgs, A, 2, 1, 32, 32, 16, 768, blend=FusedBlend(part, 2, 1.0, 0.0, (0, 0, 33, 4)))
+        ops.patchify(imgs, A, 2, 1, 32, 32, 16, 768, blend=FusedBlend(part, 2, 1.0, 0.0, (0, 0, 33, 4)))
     with pytest.raises(RuntimeError, match="mode"):
-        ops.patchify_blend(imgs, A, 2, 1, 32, 32, 16, 768, blend=FusedBlend(part, 3, 1.0, 0.0, (0, 0, 0, 0)))
+        ops.patchify(imgs, A, 2, 1, 32, 32, 16, 768, blend=FusedBlend(part, 3, 1.0, 0.0, (0, 0, 0, 0)))
     with pytest.raises(ValueError, match="one index per clip"):
-        ops.patchify_blend(imgs, A, 2, 1, 32, 32, 16, 768, blend=FusedBlend(part[:1], 1, 0.5, 0.5, (0, 0, 0, 0)))
+        ops.patchify(imgs, A, 2, 1, 32, 32, 16, 768, blend=FusedBlend(part[:1], 1, 0.5, 0.5, (0, 0, 0, 0)))
 
 
 # ---- whole training steps ----------------------------------------------------------------------------------------------

@@ -540,6 +540,27 @@ def test_patchify_and_embed(p, res):
     close(dtmp, tmp.grad, 2e-4, 1e-4, "embed_bwd dtemporal")
 
 
+def test_patchify_picks_its_entry_point():
+    """what ops.patchify decides itself: the output type comes from A.dtype (the f32 gather rounded to bf16 is the bf16
+    gather, bit for bit), bf16 clips go only into a bf16 A without a blend, and A is bf16 or f32"""
+    ops = _ops()
+    from aim_amd.blending import FusedBlend
+    H, p, Kp = 16, 8, 192
+    imgs = rnd((1, 3, 1, H, H), 69)
+    a32 = torch.full((4, Kp), float("nan"), device=DEV)
+    a16 = torch.full((4, Kp), float("nan"), dtype=torch.bfloat16, device=DEV)
+    ops.patchify(imgs, a32, 1, 1, H, H, p, Kp)
+    ops.patchify(imgs, a16, 1, 1, H, H, p, Kp)
+    assert torch.equal(a32.to(torch.bfloat16).view(torch.int16), a16.view(torch.int16))
+    ib = imgs.to(torch.bfloat16)
+    with pytest.raises(TypeError):
+        ops.patchify(ib, a32, 1, 1, H, H, p, Kp)
+    part = torch.zeros(1, dtype=torch.int32, device=DEV)
+    with pytest.raises(TypeError):
+        ops.patchify(ib, a16, 1, 1, H, H, p, Kp, blend=FusedBlend(part, 1, 0.5, 0.5, (0, 0, 0, 0)))
+    with pytest.raises(TypeError):
+        ops.patchify(imgs, a32.to(torch.float16), 1, 1, H, H, p, Kp)
+
 
 def test_cast_table():
     """aim_cast_multi: row casts (4-wide path and the scalar one), 32x32-tile transposes (and the scalar one), fp32 bias copies

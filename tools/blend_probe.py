@@ -45,8 +45,8 @@ def gather_part(dev, iters):
 
     cases = {
         "patchify": lambda: ops.patchify(imgs, A, B, T, R, R, p, Kp),
-        "fused_mixup": lambda: ops.patchify_blend(imgs, A, B, T, R, R, p, Kp, blend=fm),
-        "fused_cutmix": lambda: ops.patchify_blend(imgs, A, B, T, R, R, p, Kp, blend=fc),
+        "fused_mixup": lambda: ops.patchify(imgs, A, B, T, R, R, p, Kp, blend=fm),
+        "fused_cutmix": lambda: ops.patchify(imgs, A, B, T, R, R, p, Kp, blend=fc),
         "eager_mixup": lambda: eager(mix, pm),
         "eager_cutmix": lambda: eager(cut, pc),
     }
@@ -69,7 +69,7 @@ def gather_part(dev, iters):
     for bl, plan, fb in ((mix, pm, fm), (cut, pc, fc)):
         eager(bl, plan)
         ref.copy_(A)
-        ops.patchify_blend(imgs, A, B, T, R, R, p, Kp, blend=fb)
+        ops.patchify(imgs, A, B, T, R, R, p, Kp, blend=fb)
         out["bit_identical_" + type(bl).__name__] = bool(torch.equal(A.view(torch.int16), ref.view(torch.int16)))
     return out
 
