@@ -262,6 +262,72 @@ __device__ __forceinline__ bf16x8 pair_rows16(bf16x4 a, bf16x4 b) {
     return __builtin_bit_cast(bf16x8, u32x4_t{a0, a1, b0, b1});
 }
 
+// ---- tile idioms of the common image (16x16x32 fragments; lane = (frow = lane & 15, fq = lane >> 4)) -------------------
+
+// Stage rows [0, N) of a row-strided matrix (ld2 bytes per row) into a swizzled image: wave w takes the 8-row pieces w,
+// w + nwaves, ... below npieces; rows past N are zero-filled (AIM_OOB).  With rb / ldb2 / ib the same rows of a second matrix
+// go to a second image in the same trip.  The resource's type picks the primitive (make_rsrc: the builtin;
+// make_rsrc_words: stage_piece_asm).
+template <typename R>
+__device__ __forceinline__ void stage_rows(R ra, int lda2, AIM_LDS char* ia, int npieces, int N, int wave, int nwaves, int lane,
+                                           const R* rb = nullptr, int ldb2 = 0, AIM_LDS char* ib = nullptr) {
+    const int srow = lane >> 3, schunk = (lane & 7) ^ srow;
+    auto piece = [&](R rsrc, AIM_LDS char* img, int ld2, int p) {
+        const int r = p * 8 + srow;
+        const unsigned voff = r < N ? (unsigned)(r * ld2 + schunk * 16) : AIM_OOB;
+        if constexpr (__is_same(R, aim_rsrc_words)) stage_piece_asm(rsrc, img + p * 1024, voff);
+        else stage_piece(rsrc, img + p * 1024, voff);
+    };
+    for (int p = wave; p < npieces; p += nwaves) {
+        piece(ra, ia, lda2, p);
+        if (rb) piece(*rb, ib, ldb2, p);
+    }
+}
+
+// a row's 64 values as the two 16x16x32 row fragments of its lane quartet: k = 32 ks + 8 fq .. + 7
+__device__ __forceinline__ void load_frag(bf16x8 (&f)[2], const bf16_t* row, int fq) {
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) f[ks] = *(const bf16x8*)(row + (ks * 4 + fq) * 8);
+}
+
+// The TRANSPOSED operand: the 32 rows of block kk, columns 16 dt .. 16 dt + 15 of an image, as the fragment of a product whose
+// reduction runs over the image's ROWS (V^T, K^T, Q^T, dO^T).  ds_read_b64_tr_b16 works on 16 lanes: lane i passes the address
+// of four consecutive elements -- row (i >> 2), columns 4 (i & 3) .. + 3 of a 4 x 16 block -- and receives COLUMN i of that
+// block, rows 0 .. 3.  Column 16 dt + 4 (i & 3) is byte 32 dt + 8 (i & 3) of the row: chunk 2 dt + ((i & 3) >> 1), half
+// (i & 1) * 8; the 16-lane group fq takes the block at rows 4 fq, so the lane's row is r0 = 32 kk + 4 fq + (i >> 2).  Lane
+// (i, fq) thus holds, of column 16 dt + i, rows 32 kk + 4 fq + e (first read) and 32 kk + 16 + 4 fq + e (second read), e < 4,
+// in k positions 8 fq + e and 8 fq + 4 + e.  That is a permutation of the 32 rows over the MFMA's k positions, and the SAME
+// one that packing the accumulators of two 16-row score tiles (rows 16 t + 4 fq + e of tiles 2 kk, 2 kk + 1) into the other
+// operand gives, so the product sums every row once.  Eight consecutive rows at one chunk hit eight distinct chunk positions
+// of the image (DESIGN.md section 4 has the image's derivation).
+__device__ __forceinline__ bf16x8 tr_frag(const AIM_LDS char* img, int kk, int dt, int frow, int fq) {
+    const int r0 = kk * 32 + fq * 4 + (frow >> 2);
+    const int ch = dt * 2 + ((frow & 3) >> 1), half = (frow & 1) * 8;
+    const AIM_LDS char* p = img + swz_off(r0, ch) + half;      // (r0 + 16) & 7 == r0 & 7: 16 rows on, the same chunk position
+    return __builtin_shufflevector(lds_read_tr4(p), lds_read_tr4(p + 16 * 128), 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+// A lane's accumulator tiles hold columns 16 dt + 4 fq + e of its row.  Tiles (dt, dt + 1) leave as ONE 16-byte store
+// (pair_rows16): an even 16-lane row writes 8 consecutive columns of tile dt, an odd one 8 of tile dt + 1, so the lane's
+// store is at column tiles16_col(fq) + 16 dt of the row's 64.  Every lane calls (the swap needs all four rows); `ok` gates the store.
+__device__ __forceinline__ int tiles16_col(int fq) { return (fq & 1) ? 16 + (fq - 1) * 4 : fq * 4; }
+// tiles (dt, dt + 1) = (a, b) of the lane, scaled, as the 16 bytes that go to the row's column tiles16_col(fq) + 16 dt
+__device__ __forceinline__ bf16x8 pair_tiles16(f32x4 a, f32x4 b, float scale) {
+    a *= scale;
+    b *= scale;
+    return pair_rows16(pack4(a[0], a[1], a[2], a[3]), pack4(b[0], b[1], b[2], b[3]));
+}
+__device__ __forceinline__ void store_tiles16(bf16_t* at, f32x4 a, f32x4 b, float scale, bool ok) {
+    const bf16x8 v = pair_tiles16(a, b, scale);
+    if (ok) *(bf16x8*)at = v;
+}
+// all four tiles, `row` = the row's column 0
+__device__ __forceinline__ void store_tiles16(bf16_t* row, const f32x4 (&o)[4], float scale, bool ok, int fq) {
+    bf16_t* op = row + tiles16_col(fq);
+#pragma unroll
+    for (int dt = 0; dt < 4; dt += 2) store_tiles16(op + dt * 16, o[dt], o[dt + 1], scale, ok);
+}
+
 // XCD-aware bijective remap of a linear block id (8 XCDs, blocks dealt round-robin): blocks that
 // share an XCD get a contiguous range of logical ids (cdna guide T1, bijective form).
 __device__ __forceinline__ int xcd_remap(int bid, int nwg) {

@@ -18,21 +18,14 @@
 //        reads of the row-major Q / dO images.  dK, dV need no cross-workgroup reduction.
 // Scores are recomputed twice (7 MFMA products instead of 5) in exchange for no dS exchange through
 // LDS and no atomics; attention is ~4 % of the block's FLOPs.
-#include "aim_common.h"
+#include "attn_tile.h"
 #include "aim_kernels_internal.h"
 #include <stdlib.h>
 #include <type_traits>
 
 namespace {
 
-constexpr float LOG2E = 1.4426950408889634f;
-constexpr float C2 = 0.125f * LOG2E;      // 1/sqrt(dh) * log2(e): probabilities are recomputed in base 2
-
-// p = exp2(x) limited to [0, 1]: the limit is the clamp bit of the v_exp_f32 itself (no instruction of its own).  A true
-// probability never exceeds 1, but a key past N has a zero-filled K row, so s = 0 and x = -lse log2(e): for a query whose
-// log-sum-exp is below -88.7 (every logit strongly negative) exp2(x) is +inf, its dS is +-inf or NaN, and that times the zero
-// K^T row put NaN into dQ.  With p <= 1 the dS of such a key is finite and its zero K^T row removes it, as designed.
-__device__ __forceinline__ float prob_exp2(float x) { return __builtin_amdgcn_fmed3f(__builtin_amdgcn_exp2f(x), 0.f, 1.f); }
+using namespace attn_tile;
 
 // SHIFT (all three kernels of this file's full backward): the head-shifted form, aim_attn_bwd_shift.  An item is still the
 // QUERIES of (frame bt, head h); its K and V are read from frame attn_kv_frame(sh, bt, h) of the same clip and its dK and dV are
@@ -57,13 +50,7 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_dq_kernel(const bf16_t* __res
         const bf16_t* kvb = SHIFT ? qkv + (long long)attn_kv_frame(sh, bt, h) * N * ld + h * 64 : base;
         __amdgpu_buffer_rsrc_t rK = make_rsrc(kvb + D, ((long long)(N - 1) * ld + 64) * 2);
         __amdgpu_buffer_rsrc_t rV = make_rsrc(kvb + 2 * D, ((long long)(N - 1) * ld + 64) * 2);
-        const int srow = lane >> 3, schunk = (lane & 7) ^ srow;
-        for (int p = wave; p < nkt * 2; p += 8) {
-            const int key = p * 8 + srow;
-            const unsigned voff = key < N ? (unsigned)((key * ld + schunk * 8) * 2) : AIM_OOB;
-            stage_piece(rK, sK + p * 1024, voff);
-            stage_piece(rV, sV + p * 1024, voff);
-        }
+        stage_rows(rK, ld * 2, sK, nkt * 2, N, wave, 8, lane, &rV, ld * 2, sV);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -73,18 +60,16 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_dq_kernel(const bf16_t* __res
         asm volatile("" ::: "memory");          // keep the (qt-invariant) K/V fragment reads inside the loop
         const int q = qt * 16 + frow;
         const int qc = q < N ? q : N - 1;
-        bf16x8 qf[2], dof[2];
+        bf16x8 qf[2], dof[2], of[2];
+        const long long orow = ((long long)bt * N + qc) * D + h * 64;
+        load_frag(qf, base + (long long)qc * ld, fq);
+        load_frag(dof, dout + orow, fq);
+        load_frag(of, out + orow, fq);
         float dl = 0.f;
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            const int c = (ks * 4 + fq) * 8;
-            qf[ks] = *(const bf16x8*)(base + (long long)qc * ld + c);
-            const long long orow = ((long long)bt * N + qc) * D + h * 64 + c;
-            dof[ks] = *(const bf16x8*)(dout + orow);
-            const bf16x8 of = *(const bf16x8*)(out + orow);
+        for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-            for (int e = 0; e < 8; ++e) dl += (float)dof[ks][e] * (float)of[e];
-        }
+            for (int e = 0; e < 8; ++e) dl += (float)dof[ks][e] * (float)of[ks][e];
         dl += __shfl_xor(dl, 16, 64);
         dl += __shfl_xor(dl, 32, 64);
         // exp(s/8 - L) = exp2(s * C2 - L2): one fma + one v_exp per score
@@ -94,53 +79,9 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_dq_kernel(const bf16_t* __res
         f32x4 dq[4];
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) dq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-        for (int kk = 0; kk < nkt / 2; ++kk) {
-            bf16x8 dsf;
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const int t = 2 * kk + u;
-                // the dP accumulators start from -delta (this lane's query): dS = P o (dP - delta) without the subtraction
-                f32x4 s = f32x4{0.f, 0.f, 0.f, 0.f}, dp = f32x4{-dl, -dl, -dl, -dl};
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks) {
-                    const bf16x8 kf = lds_read8(sK + swz_off(t * 16 + frow, ks * 4 + fq));
-                    const bf16x8 vf = lds_read8(sV + swz_off(t * 16 + frow, ks * 4 + fq));
-                    s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[ks], s, 0, 0, 0);
-                    dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, dof[ks], dp, 0, 0, 0);
-                }
-                // No key mask: rows of K and V past N are zero-filled in LDS, so such a key has a finite p (prob_exp2: at
-                // most 1) and its dS meets a zero K^T row in the dQ product.  The 1/sqrt(dh) factor of dS is applied once to dQ.
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float p = prob_exp2(s[e] * C2 - L2);
-                    dsf[u * 4 + e] = (bf16_t)(p * dp[e]);
-                }
-            }
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt) {
-                const int r0 = (2 * kk) * 16 + fq * 4 + (frow >> 2);
-                const int ch = dt * 2 + ((frow & 3) >> 1), half = (frow & 1) * 8;
-                const bf16x4 a = lds_read_tr4(sK + swz_off(r0, ch) + half);
-                const bf16x4 b = lds_read_tr4(sK + swz_off(r0 + 16, ch) + half);
-                bf16x8 ktf;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    ktf[e] = a[e];
-                    ktf[4 + e] = b[e];
-                }
-                dq[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ktf, dsf, dq[dt], 0, 0, 0);
-            }
-        }
-        {   // 16-byte stores: tiles (dt, dt+1) paired across even / odd 16-lane rows (aim_common.h pair_rows16)
-            bf16_t* op = dqkv + ((long long)bt * N + (q < N ? q : 0)) * ld + h * 64 + ((fq & 1) ? 16 + (fq - 1) * 4 : fq * 4);
-#pragma unroll
-            for (int dt = 0; dt < 4; dt += 2) {
-                const bf16x8 v = pair_rows16(
-                    pack4(dq[dt][0] * 0.125f, dq[dt][1] * 0.125f, dq[dt][2] * 0.125f, dq[dt][3] * 0.125f),
-                    pack4(dq[dt + 1][0] * 0.125f, dq[dt + 1][1] * 0.125f, dq[dt + 1][2] * 0.125f, dq[dt + 1][3] * 0.125f));
-                if (q < N) *(bf16x8*)(op + dt * 16) = v;
-            }
-        }
+        for (int kk = 0; kk < nkt / 2; ++kk)
+            dq_key_pair(dq, sK, sV, kk, qf, dof, dl, L2, frow, fq, [](int, bf16_t, bf16_t) {});
+        store_tiles16(dqkv + ((long long)bt * N + (q < N ? q : 0)) * ld + h * 64, dq, 0.125f, q < N, fq);
     }
 }
 
@@ -167,12 +108,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const bf16_t* __re
     {
         __amdgpu_buffer_rsrc_t rQ = make_rsrc(base, ((long long)(N - 1) * ld + 64) * 2);
         __amdgpu_buffer_rsrc_t rO = make_rsrc(dob, ((long long)(N - 1) * D + 64) * 2);
-        const int srow = lane >> 3, schunk = (lane & 7) ^ srow;
-        for (int p = wave; p < nq32 / 8; p += 4) {
-            const int qr = p * 8 + srow;
-            stage_piece(rQ, sQ + p * 1024, qr < N ? (unsigned)((qr * ld + schunk * 8) * 2) : AIM_OOB);
-            stage_piece(rO, sO + p * 1024, qr < N ? (unsigned)((qr * D + schunk * 8) * 2) : AIM_OOB);
-        }
+        stage_rows(rQ, ld * 2, sQ, nq32 / 8, N, wave, 4, lane, &rO, D * 2, sO);
         for (int i = tid; i < nq32; i += 256) {
             sL[i] = i < N ? lse[((long long)bt * H + h) * N + i] * LOG2E : 0.f;
             sD[i] = i < N ? -delta[((long long)bt * H + h) * N + i] : 0.f;      // negated: the dP accumulators start from it
@@ -188,11 +124,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const bf16_t* __re
         for (int u = 0; u < 2; ++u) {
             const int key = kp * 32 + u * 16 + frow;
             const int kc = key < N ? key : N - 1;
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                kf[u][ks] = *(const bf16x8*)(kvb + (long long)kc * ld + D + (ks * 4 + fq) * 8);
-                vf[u][ks] = *(const bf16x8*)(kvb + (long long)kc * ld + 2 * D + (ks * 4 + fq) * 8);
-            }
+            load_frag(kf[u], kvb + (long long)kc * ld + D, fq);
+            load_frag(vf[u], kvb + (long long)kc * ld + 2 * D, fq);
         }
         f32x4 dk[4][2], dv[4][2];
 #pragma unroll
@@ -227,15 +160,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const bf16_t* __re
             }
         };
         auto step = [&](int qs, RowSet& cur, bool more) {
-            bf16x4 ta[4], tb[4], tc[4], td[4];
+            bf16x8 qt8[4], ot8[4];
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt) {
-                const int r0 = qs * 32 + fq * 4 + (frow >> 2);
-                const int ch = dt * 2 + ((frow & 3) >> 1), half = (frow & 1) * 8;
-                ta[dt] = lds_read_tr4(sQ + swz_off(r0, ch) + half);
-                tb[dt] = lds_read_tr4(sQ + swz_off(r0 + 16, ch) + half);
-                tc[dt] = lds_read_tr4(sO + swz_off(r0, ch) + half);
-                td[dt] = lds_read_tr4(sO + swz_off(r0 + 16, ch) + half);
+                qt8[dt] = tr_frag(sQ, qs, dt, frow, fq);
+                ot8[dt] = tr_frag(sO, qs, dt, frow, fq);
             }
             __builtin_amdgcn_sched_barrier(0);          // keep the requests up here: the scheduler would sink them to their uses
             bf16x8 pf[2], dsf[2];
@@ -264,21 +193,12 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const bf16_t* __re
             if (more) load_rows(qs + 1, cur);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int dt = 0; dt < 4; ++dt) {
-                bf16x8 qt8, ot8;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    qt8[e] = ta[dt][e];
-                    qt8[4 + e] = tb[dt][e];
-                    ot8[e] = tc[dt][e];
-                    ot8[4 + e] = td[dt][e];
-                }
+            for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
                 for (int u = 0; u < 2; ++u) {
-                    dv[dt][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ot8, pf[u], dv[dt][u], 0, 0, 0);
-                    dk[dt][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qt8, dsf[u], dk[dt][u], 0, 0, 0);
+                    dv[dt][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ot8[dt], pf[u], dv[dt][u], 0, 0, 0);
+                    dk[dt][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qt8[dt], dsf[u], dk[dt][u], 0, 0, 0);
                 }
-            }
         };
         {
             const int nsteps = nq32 / 32;
@@ -289,15 +209,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const bf16_t* __re
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             const int key = kp * 32 + u * 16 + frow;
-            // 16-byte stores: tiles (dt, dt+1) paired across even / odd 16-lane rows (aim_common.h pair_rows16)
-            bf16_t* op = dqkv + ((long long)kvbt * N + (key < N ? key : 0)) * ld + h * 64 + ((fq & 1) ? 16 + (fq - 1) * 4 : fq * 4);
+            bf16_t* op = dqkv + ((long long)kvbt * N + (key < N ? key : 0)) * ld + h * 64 + tiles16_col(fq);
 #pragma unroll
             for (int dt = 0; dt < 4; dt += 2) {
-                const bf16x8 vk = pair_rows16(
-                    pack4(dk[dt][u][0] * 0.125f, dk[dt][u][1] * 0.125f, dk[dt][u][2] * 0.125f, dk[dt][u][3] * 0.125f),
-                    pack4(dk[dt + 1][u][0] * 0.125f, dk[dt + 1][u][1] * 0.125f, dk[dt + 1][u][2] * 0.125f, dk[dt + 1][u][3] * 0.125f));
-                const bf16x8 vv = pair_rows16(pack4(dv[dt][u][0], dv[dt][u][1], dv[dt][u][2], dv[dt][u][3]),
-                                              pack4(dv[dt + 1][u][0], dv[dt + 1][u][1], dv[dt + 1][u][2], dv[dt + 1][u][3]));
+                const bf16x8 vk = pair_tiles16(dk[dt][u], dk[dt + 1][u], 0.125f), vv = pair_tiles16(dv[dt][u], dv[dt + 1][u], 1.0f);
                 if (key < N) {
                     *(bf16x8*)(op + D + dt * 16) = vk;
                     *(bf16x8*)(op + 2 * D + dt * 16) = vv;
@@ -472,15 +387,7 @@ __global__ __launch_bounds__(512) void attn_bwd_pipe_kernel(const bf16_t* __rest
     auto finish_delta = [&](const PfPos& p, AIM_LDS float* sl) {
 #pragma unroll
         for (int g = 0; g < 8; ++g) {
-            const bf16x8 o8 = __builtin_bit_cast(bf16x8, acc[g]), d8 = __builtin_bit_cast(bf16x8, acc[8 + g]);
-            float dl = 0.f;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) dl += (float)d8[e] * (float)o8[e];
-            // sum over the row's 8 lanes with DPP (quad_perm xor 1, xor 2, then row_half_mirror: the other quad of the eight);
-            // the ds_bpermute form of __shfl_xor made this wave the tick's critical path
-            dl += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, dl), 0xB1, 0xF, 0xF, true));
-            dl += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, dl), 0x4E, 0xF, 0xF, true));
-            dl += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, dl), 0x141, 0xF, 0xF, true));
+            const float dl = row_dot8(__builtin_bit_cast(bf16x8, acc[8 + g]), __builtin_bit_cast(bf16x8, acc[g]));
             // stored NEGATED: the producers start the dP accumulators from -delta, so dS = P o dP needs no subtraction
             if ((lane & 7) == 0) sl[64 + g * 8 + srow] = p.qb * 64 + g * 8 + srow < N ? -dl : 0.f;
         }
@@ -488,13 +395,7 @@ __global__ __launch_bounds__(512) void attn_bwd_pipe_kernel(const bf16_t* __rest
         if (XT && p.qb == nqb - 1) {
 #pragma unroll
             for (int g = 0; g < 2; ++g) {
-                const bf16x8 o8 = vfn[g][0], d8 = vfn[g][1];
-                float dl = 0.f;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) dl += (float)d8[e] * (float)o8[e];
-                dl += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, dl), 0xB1, 0xF, 0xF, true));
-                dl += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, dl), 0x4E, 0xF, 0xF, true));
-                dl += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, dl), 0x141, 0xF, 0xF, true));
+                const float dl = row_dot8(vfn[g][1], vfn[g][0]);
                 if ((lane & 7) == 0) sXLD[16 + g * 8 + srow] = xq0 + g * 8 + srow < N ? -dl : 0.f;
             }
             if (lane < 16) sXLD[lane] = xq0 + lane < N ? lregx * LOG2E : 0.f;
@@ -504,19 +405,14 @@ __global__ __launch_bounds__(512) void attn_bwd_pipe_kernel(const bf16_t* __rest
         const bf16_t* base = qkv + (long long)kvf(p) * N * ld + p.h * 64;
         const aim_rsrc_words rK = make_rsrc_words(base + D, ((long long)(N - 1) * ld + 64) * 2);
         AIM_LDS char* img = sKimg + (p.k & 1) * nrow * 128;
-        for (int pc = wave; pc < nrow / 8; pc += 8) {
-            const int r = pc * 8 + srow;
-            stage_piece_asm(rK, img + pc * 1024, r < N ? (unsigned)((r * ld + schunk * 8) * 2) : AIM_OOB);
-        }
+        stage_rows(rK, ld * 2, img, nrow / 8, N, wave, 8, lane);
     };
     auto issue_v = [&](const PfPos& p) {        // producers: V row fragments of an item -> vfn
         const bf16_t* base = qkv + (long long)kvf(p) * N * ld + p.h * 64;
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             const int key = wave * 32 + u * 16 + frow;
-            const int kc = key < N ? key : N - 1;
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) vfn[u][ks] = *(const bf16x8*)(base + (long long)kc * ld + 2 * D + (ks * 4 + fq) * 8);
+            load_frag(vfn[u], base + (long long)(key < N ? key : N - 1) * ld + 2 * D, fq);
         }
     };
 
@@ -524,13 +420,11 @@ __global__ __launch_bounds__(512) void attn_bwd_pipe_kernel(const bf16_t* __rest
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             const int key = wave * 32 + u * 16 + frow;
-            bf16_t* op = dqkv + ((long long)kvf(p) * N + (key < N ? key : 0)) * ld + p.h * 64 + ((fq & 1) ? 16 + (fq - 1) * 4 : fq * 4);
+            bf16_t* op = dqkv + ((long long)kvf(p) * N + (key < N ? key : 0)) * ld + p.h * 64 + tiles16_col(fq);
 #pragma unroll
             for (int dt = 0; dt < 4; dt += 2) {
-                const f32x4 k0 = acc[dt * 2 + u] * 0.125f, k1 = acc[(dt + 1) * 2 + u] * 0.125f;
-                const f32x4 v0 = acc[8 + dt * 2 + u], v1 = acc[8 + (dt + 1) * 2 + u];
-                const bf16x8 vk = pair_rows16(pack4(k0[0], k0[1], k0[2], k0[3]), pack4(k1[0], k1[1], k1[2], k1[3]));
-                const bf16x8 vv = pair_rows16(pack4(v0[0], v0[1], v0[2], v0[3]), pack4(v1[0], v1[1], v1[2], v1[3]));
+                const bf16x8 vk = pair_tiles16(acc[dt * 2 + u], acc[(dt + 1) * 2 + u], 0.125f);
+                const bf16x8 vv = pair_tiles16(acc[8 + dt * 2 + u], acc[8 + (dt + 1) * 2 + u], 1.0f);
                 if (key < N) {
                     *(bf16x8*)(op + D + dt * 16) = vk;
                     *(bf16x8*)(op + 2 * D + dt * 16) = vv;
@@ -669,12 +563,9 @@ __global__ __launch_bounds__(512) void attn_bwd_pipe_kernel(const bf16_t* __rest
                 const int chq = qt * 2 + ((frow & 3) >> 1), half = (frow & 1) * 8;
                 const int chk0 = dt0 * 2 + ((frow & 3) >> 1), chk1 = chk0 + 2;
                 dq_keys([&](int r) { return ds_img + swz_off(r, chq) + half; }, sK, chk0, chk1, half, fq * 4 + (frow >> 2), dq0, dq1);
-                // lane holds dQ[q][d = 16 dt + 4 fq + e]; tiles (dt0, dt0+1) paired across even / odd 16-lane rows: 16-byte stores
                 const int q = prv.qb * 64 + qt * 16 + frow;
-                bf16_t* op = dqkv + ((long long)prv.bt * N + (q < N ? q : 0)) * ld + prv.h * 64 + ((fq & 1) ? 16 + (fq - 1) * 4 : fq * 4);
-                const f32x4 a = dq0 * 0.125f, b = dq1 * 0.125f;
-                const bf16x8 v = pair_rows16(pack4(a[0], a[1], a[2], a[3]), pack4(b[0], b[1], b[2], b[3]));
-                if (q < N) *(bf16x8*)(op + dt0 * 16) = v;
+                bf16_t* op = dqkv + ((long long)prv.bt * N + (q < N ? q : 0)) * ld + prv.h * 64 + tiles16_col(fq);
+                store_tiles16(op + dt0 * 16, dq0, dq1, 0.125f, q < N);
             }
             if (XT && prv.qb == nqb - 1 && (wave >> 1) == 1) {
                 // dQ of the extra tile of chunk T-1: waves 2 and 3, two d tiles each.  (Not wave 7: at an item's first tick its
@@ -689,10 +580,8 @@ __global__ __launch_bounds__(512) void attn_bwd_pipe_kernel(const bf16_t* __rest
                 const int chk0 = dt0 * 2 + ((frow & 3) >> 1), chk1 = chk0 + 2;
                 dq_keys([&](int r) { return sXDS + r * 32 + xoff; }, sK, chk0, chk1, half, fq * 4 + (frow >> 2), dq0, dq1);
                 const int q = xq0 + frow;
-                bf16_t* op = dqkv + ((long long)prv.bt * N + (q < N ? q : 0)) * ld + prv.h * 64 + ((fq & 1) ? 16 + (fq - 1) * 4 : fq * 4);
-                const f32x4 a = dq0 * 0.125f, b = dq1 * 0.125f;
-                const bf16x8 v = pair_rows16(pack4(a[0], a[1], a[2], a[3]), pack4(b[0], b[1], b[2], b[3]));
-                if (q < N) *(bf16x8*)(op + dt0 * 16) = v;
+                bf16_t* op = dqkv + ((long long)prv.bt * N + (q < N ? q : 0)) * ld + prv.h * 64 + tiles16_col(fq);
+                store_tiles16(op + dt0 * 16, dq0, dq1, 0.125f, q < N);
             }
         }
         if (producer && live) {
@@ -713,15 +602,11 @@ __global__ __launch_bounds__(512) void attn_bwd_pipe_kernel(const bf16_t* __rest
 #pragma unroll
             for (int hs = 0; hs < 2; ++hs) {
                 if ((cur.qb * 2 + hs) * 32 >= nrow) break;       // the item's last 32-query step may be its chunk's first
-                bf16x4 ta[4], tb[4], tc[4], td[4];
+                bf16x8 qt8[4], ot8[4];
 #pragma unroll
                 for (int dt = 0; dt < 4; ++dt) {
-                    const int r0 = hs * 32 + fq * 4 + (frow >> 2);
-                    const int ch = dt * 2 + ((frow & 3) >> 1), half = (frow & 1) * 8;
-                    ta[dt] = lds_read_tr4(sQ + swz_off(r0, ch) + half);
-                    tb[dt] = lds_read_tr4(sQ + swz_off(r0 + 16, ch) + half);
-                    tc[dt] = lds_read_tr4(sO + swz_off(r0, ch) + half);
-                    td[dt] = lds_read_tr4(sO + swz_off(r0 + 16, ch) + half);
+                    qt8[dt] = tr_frag(sQ, hs, dt, frow, fq);
+                    ot8[dt] = tr_frag(sO, hs, dt, frow, fq);
                 }
                 bf16x8 pf[2] = {}, dsf[2] = {};
 #pragma unroll
@@ -761,21 +646,12 @@ __global__ __launch_bounds__(512) void attn_bwd_pipe_kernel(const bf16_t* __rest
                     }
                 }
 #pragma unroll
-                for (int dt = 0; dt < 4; ++dt) {
-                    bf16x8 qt8, ot8;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        qt8[e] = ta[dt][e];
-                        qt8[4 + e] = tb[dt][e];
-                        ot8[e] = tc[dt][e];
-                        ot8[4 + e] = td[dt][e];
-                    }
+                for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
                     for (int u = 0; u < 2; ++u) {
-                        acc[8 + dt * 2 + u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ot8, pf[u], acc[8 + dt * 2 + u], 0, 0, 0);   // dV
-                        acc[dt * 2 + u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qt8, dsf[u], acc[dt * 2 + u], 0, 0, 0);         // dK
+                        acc[8 + dt * 2 + u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ot8[dt], pf[u], acc[8 + dt * 2 + u], 0, 0, 0);   // dV
+                        acc[dt * 2 + u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qt8[dt], dsf[u], acc[dt * 2 + u], 0, 0, 0);         // dK
                     }
-                }
             }
             if (XT && cur.qb == nqb - 1) {
                 // the extra tile: one 16-query half step (the upper 16 k-positions of the dV / dK products are zero)
@@ -859,10 +735,9 @@ __global__ __launch_bounds__(512) void attn_bwd_pipe_kernel(const bf16_t* __rest
 // class row only (the head reads nothing else).  dO, O and the log-sum-exp come compact ([BT, D], [BT, H]); the whole
 // dqkv [BT N, 3 D] is written: dK, dV of every key, dQ in the class row and explicit zeros in every other dQ row (the QKV
 // dgrad reads all of it).  The q part of the other rows of qkv is never read.
-// The arithmetic of the class query is the full kernels', product for product: wave 0 runs the first query tile of the dq
-// kernel above with every query but the first zeroed (S^T = K Q^T, dP^T - delta = V dO^T from -delta, p = exp2(s C2 - L2),
-// dS = bf16(p (dP - delta)), dQ^T += K^T dS^T over 32 keys per MFMA in ascending order), delta = dO . O is summed as the
-// pipelined kernel sums it (8 lanes x 8 elements, DPP tree), and with a single non-zero query a key's dK = bf16(dS) q / 8 and
+// The arithmetic of the class query is the full kernels', product for product: wave 0 runs the dq kernel's own key-pair step
+// (attn_tile.h dq_key_pair) on the first query tile with every query but the first zeroed, delta = dO . O is summed as the
+// pipelined kernel sums it (row_dot8), and with a single non-zero query a key's dK = bf16(dS) q / 8 and
 // dV = bf16(p) dO are one exact product each -- what the matrix kernels' fp32 sums hold for it.  bf16(p) and bf16(dS) of
 // every key cross LDS once; then all eight waves write the rows: the kernel is bound by that traffic (K and V read once,
 // three times as much written).  One workgroup per item, no atomics, nothing summed across workgroups.
@@ -885,18 +760,12 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_cls_kernel(const bf16_t* __re
     {
         __amdgpu_buffer_rsrc_t rK = make_rsrc(base + D, ((long long)(N - 1) * ld + 64) * 2);
         __amdgpu_buffer_rsrc_t rV = make_rsrc(base + 2 * D, ((long long)(N - 1) * ld + 64) * 2);
-        const int srow = lane >> 3, schunk = (lane & 7) ^ srow;
-        for (int p = wave; p < nkt * 2; p += 8) {
-            const int key = p * 8 + srow;
-            const unsigned voff = key < N ? (unsigned)((key * ld + schunk * 8) * 2) : AIM_OOB;
-            stage_piece(rK, sK + p * 1024, voff);
-            stage_piece(rV, sV + p * 1024, voff);
-        }
+        stage_rows(rK, ld * 2, sK, nkt * 2, N, wave, 8, lane, &rV, ld * 2, sV);
     }
     // every lane: its 16-byte chunk of q and dO (the write phase's factors) and delta, eight lanes to the row
     const int sub = lane & 7;
     float qw[8], dw[8];
-    float dl = 0.f;
+    float dl;
     {
         const bf16x8 q8 = *(const bf16x8*)(base + sub * 8);
         const bf16x8 d8 = *(const bf16x8*)(dout + crow + sub * 8);
@@ -906,78 +775,27 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_cls_kernel(const bf16_t* __re
             qw[e] = (float)q8[e];
             dw[e] = (float)d8[e];
         }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) dl += (float)d8[e] * (float)o8[e];
-        dl += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, dl), 0xB1, 0xF, 0xF, true));
-        dl += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, dl), 0x4E, 0xF, 0xF, true));
-        dl += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, dl), 0x141, 0xF, 0xF, true));
+        dl = row_dot8(d8, o8);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
     if (wave == 0) {
         // the first query tile with the class query in column 0 and zeros in the other fifteen
-        bf16x8 qf[2], dof[2];
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            const int c = (ks * 4 + fq) * 8;
-            const bf16x8 z8 = {};
-            qf[ks] = z8;
-            dof[ks] = z8;
-            if (frow == 0) {
-                qf[ks] = *(const bf16x8*)(base + c);
-                dof[ks] = *(const bf16x8*)(dout + crow + c);
-            }
+        bf16x8 qf[2] = {}, dof[2] = {};
+        if (frow == 0) {
+            load_frag(qf, base, fq);
+            load_frag(dof, dout + crow, fq);
         }
         const float L2 = lse[(long long)bt * H + h] * LOG2E;
         f32x4 dq[4];
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) dq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-        for (int kk = 0; kk < nkt / 2; ++kk) {
-            bf16x8 dsf;
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const int t = 2 * kk + u;
-                f32x4 s = f32x4{0.f, 0.f, 0.f, 0.f}, dp = f32x4{-dl, -dl, -dl, -dl};
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks) {
-                    const bf16x8 kf = lds_read8(sK + swz_off(t * 16 + frow, ks * 4 + fq));
-                    const bf16x8 vf = lds_read8(sV + swz_off(t * 16 + frow, ks * 4 + fq));
-                    s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[ks], s, 0, 0, 0);
-                    dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, dof[ks], dp, 0, 0, 0);
-                }
-                // keys past N: zero-filled K and V rows, a finite p (prob_exp2) and a zero K^T row in the dQ product
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float p = prob_exp2(s[e] * C2 - L2);
-                    const bf16_t pb = (bf16_t)p, db = (bf16_t)(p * dp[e]);
-                    dsf[u * 4 + e] = db;
-                    if (frow == 0) sPD[t * 16 + fq * 4 + e] = f32x2{(float)pb, (float)db};
-                }
-            }
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt) {
-                const int r0 = (2 * kk) * 16 + fq * 4 + (frow >> 2);
-                const int ch = dt * 2 + ((frow & 3) >> 1), half = (frow & 1) * 8;
-                const bf16x4 a = lds_read_tr4(sK + swz_off(r0, ch) + half);
-                const bf16x4 b = lds_read_tr4(sK + swz_off(r0 + 16, ch) + half);
-                bf16x8 ktf;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    ktf[e] = a[e];
-                    ktf[4 + e] = b[e];
-                }
-                dq[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ktf, dsf, dq[dt], 0, 0, 0);
-            }
-        }
-        bf16_t* op = dqkv + (long long)bt * N * ld + h * 64 + ((fq & 1) ? 16 + (fq - 1) * 4 : fq * 4);
-#pragma unroll
-        for (int dt = 0; dt < 4; dt += 2) {
-            const bf16x8 v = pair_rows16(
-                pack4(dq[dt][0] * 0.125f, dq[dt][1] * 0.125f, dq[dt][2] * 0.125f, dq[dt][3] * 0.125f),
-                pack4(dq[dt + 1][0] * 0.125f, dq[dt + 1][1] * 0.125f, dq[dt + 1][2] * 0.125f, dq[dt + 1][3] * 0.125f));
-            if (frow == 0) *(bf16x8*)(op + dt * 16) = v;
-        }
+        for (int kk = 0; kk < nkt / 2; ++kk)
+            dq_key_pair(dq, sK, sV, kk, qf, dof, dl, L2, frow, fq, [&](int key, bf16_t pb, bf16_t db) {
+                if (frow == 0) sPD[key] = f32x2{(float)pb, (float)db};
+            });
+        store_tiles16(dqkv + (long long)bt * N * ld + h * 64, dq, 0.125f, frow == 0, fq);
     }
     __syncthreads();
     // every wave: the rows.  64 keys per trip, 8 lanes x 16 bytes per 64-wide row part

@@ -11,7 +11,7 @@
 // P^T accumulators are, unchanged, the second operand of  O^T = V^T P^T  (V^T fragments come from
 // the row-major V image through ds_read_b64_tr_b16).  O^T puts 4 consecutive head-dim elements of a
 // query in one lane: 8-byte stores into the merged-heads [M, D] layout.
-#include "aim_common.h"
+#include "attn_tile.h"
 #include "aim_kernels_internal.h"
 
 #ifdef AIM_X_STAMPS      // diagnostic build only (tools/probe_attn.py): shader-clock stamps of one workgroup's waves
@@ -23,6 +23,8 @@ extern "C" int aim_attn_probe(void* buf) { g_attn_probe = (unsigned long long*)b
 #endif
 
 namespace {
+
+using namespace attn_tile;
 
 // NKT: number of 16-key tiles of the LDS images (even).  NFULL: key tiles below NFULL are known to lie entirely below N,
 // so only tiles >= NFULL carry masking code (N = 197: NKT = 14, NFULL = 12; masking every tile costs ~1.5x the
@@ -58,7 +60,6 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_kernel(const bf16_t* __restri
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int frow = lane & 15, fq = lane >> 4;
     constexpr int NW = 8;                      // waves per workgroup
-    const float C2 = 0.125f * 1.4426950408889634f;   // 1/sqrt(dh) * log2(e): softmax runs in base 2
 
     const bf16_t* base = qkv + (long long)bt * N * ld + h * 64;
     const int nqt = CLS ? 1 : (N + 15) >> 4;
@@ -66,21 +67,13 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_kernel(const bf16_t* __restri
     bf16x8 qf[2];
     {
         const int q0 = wave * 16 + frow;
-        const int qc = q0 < N ? q0 : N - 1;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) qf[ks] = *(const bf16x8*)(base + (long long)qc * ld + (ks * 4 + fq) * 8);
+        load_frag(qf, base + (long long)(q0 < N ? q0 : N - 1) * ld, fq);
     }
     {
         const bf16_t* kvb = SHIFT ? qkv + (long long)attn_kv_frame(sh, bt, h) * N * ld + h * 64 : base;
         __amdgpu_buffer_rsrc_t rK = make_rsrc(kvb + D, ((long long)(N - 1) * ld + 64) * 2);
         __amdgpu_buffer_rsrc_t rV = make_rsrc(kvb + 2 * D, ((long long)(N - 1) * ld + 64) * 2);
-        const int srow = lane >> 3, schunk = (lane & 7) ^ srow;
-        for (int p = wave; p < NKT * 2; p += NW) {
-            const int key = p * 8 + srow;
-            const unsigned voff = key < N ? (unsigned)((key * ld + schunk * 8) * 2) : AIM_OOB;
-            stage_piece(rK, sK + p * 1024, voff);
-            stage_piece(rV, sV + p * 1024, voff);
-        }
+        stage_rows(rK, ld * 2, sK, NKT * 2, N, wave, NW, lane, &rV, ld * 2, sV);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     ATT_STAMP(1);
@@ -100,22 +93,12 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_kernel(const bf16_t* __restri
 #endif
         ATT_STAMPQ(0);
         f32x4 s[NKT];
-#pragma unroll
-        for (int t = 0; t < NKT; ++t) {
-            s[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                const bf16x8 kf = lds_read8(sK + swz_off(t * 16 + frow, ks * 4 + fq));
-                s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[ks], s[t], 0, 0, 0);
-            }
-        }
+        tile_scores(s, sK, qf, frow, fq);
         ATT_STAMPQ(1);
         // prefetch the next query tile of this wave
         if (qt + NW < nqt) {
             const int qn = (qt + NW) * 16 + frow;
-            const int qc = qn < N ? qn : N - 1;
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) qf[ks] = *(const bf16x8*)(base + (long long)qc * ld + (ks * 4 + fq) * 8);
+            load_frag(qf, base + (long long)(qn < N ? qn : N - 1) * ld, fq);
         }
         // softmax over keys (lane holds keys t*16 + fq*4 + e of query lane&15); only tiles that straddle N mask
         float mx = -INFINITY;
@@ -152,31 +135,7 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_kernel(const bf16_t* __restri
         f32x4 o[4];
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kk = 0; kk < NKT / 2; ++kk) {
-            bf16x8 pf;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                pf[e] = (bf16_t)s[2 * kk][e];
-                pf[4 + e] = (bf16_t)s[2 * kk + 1][e];
-            }
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt) {
-                // V^T fragment: rows key0 + (i>>2), columns dt*16 + 4*(i&3) .. +3 of the V image (i = lane&15)
-                const int r0 = (2 * kk) * 16 + fq * 4 + (frow >> 2);
-                const int r1 = r0 + 16;
-                const int ch = dt * 2 + ((frow & 3) >> 1), half = (frow & 1) * 8;
-                const bf16x4 v0 = lds_read_tr4(sV + swz_off(r0, ch) + half);
-                const bf16x4 v1 = lds_read_tr4(sV + swz_off(r1, ch) + half);
-                bf16x8 vf;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    vf[e] = v0[e];
-                    vf[4 + e] = v1[e];
-                }
-                o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf, o[dt], 0, 0, 0);
-            }
-        }
+        tile_accum(o, sV, s, frow, fq);      // O^T += V^T P^T
         ATT_STAMPQ(3);
         if constexpr (OUT8) {
             // fp8 bytes: the lane owns 4 consecutive head-dim elements of tile dt -> one 4-byte store each
@@ -185,16 +144,8 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_kernel(const bf16_t* __restri
             for (int dt = 0; dt < 4; ++dt)
                 if (q < N) *(unsigned*)(op8 + dt * 16) = pack4_fp8(o[dt][0] * inv, o[dt][1] * inv, o[dt][2] * inv, o[dt][3] * inv);
         } else {
-            // 16-byte stores: tiles (dt, dt+1) are paired across the even / odd 16-lane rows (aim_common.h pair_rows16), so a
-            // lane writes 8 consecutive head-dim elements and a row's four lanes cover 64 contiguous bytes
             const long long orow = CLS ? (long long)bt : (long long)bt * N + (q < N ? q : 0);
-            bf16_t* op = out + orow * D + h * 64 + ((fq & 1) ? 16 + (fq - 1) * 4 : fq * 4);
-#pragma unroll
-            for (int dt = 0; dt < 4; dt += 2) {
-                const bf16x8 v = pair_rows16(pack4(o[dt][0] * inv, o[dt][1] * inv, o[dt][2] * inv, o[dt][3] * inv),
-                                             pack4(o[dt + 1][0] * inv, o[dt + 1][1] * inv, o[dt + 1][2] * inv, o[dt + 1][3] * inv));
-                if (CLS ? q == 0 : q < N) *(bf16x8*)(op + dt * 16) = v;
-            }
+            store_tiles16(out + orow * D + h * 64, o, inv, CLS ? q == 0 : q < N, fq);
         }
         ATT_STAMPQ(4);
     }

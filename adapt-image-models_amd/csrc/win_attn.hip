@@ -33,14 +33,14 @@
 // tokens past S load the window's last token and are not stored.
 #include <stdio.h>
 
-#include "aim_common.h"
+#include "attn_tile.h"
 #include "aim_kernels_internal.h"
 
 namespace {
 
+using namespace attn_tile;
+
 constexpr int WIN_MAX_S = AIM_WIN_ATTN_MAX_S;
-constexpr float LOG2E = 1.4426950408889634f;
-constexpr float C2 = 0.125f * LOG2E;      // 1/sqrt(dh) * log2(e): the softmax runs in base 2
 constexpr int WIN_PLAIN = 0, WIN_WRAP = 1, WIN_CUT = 2;
 
 struct WinGeom {
@@ -128,21 +128,9 @@ __device__ __forceinline__ void stage_pair(__amdgpu_buffer_rsrc_t ra, int lda2, 
     }
 }
 
-// s[t][e] = sum_d img[t 16 + fq 4 + e][d] * x[lane & 15][d] for the 64 rows of an image
-__device__ __forceinline__ void tile_scores(f32x4 (&s)[4], const AIM_LDS char* img, const bf16x8 (&xf)[2], int frow, int fq) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        s[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            const bf16x8 af = lds_read8(img + swz_off(t * 16 + frow, ks * 4 + fq));
-            s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, xf[ks], s[t], 0, 0, 0);
-        }
-    }
-}
-
-// o[dt][e] += sum_rows img[row][dt 16 + fq 4 + e] * bf16(w[row]) over the 64 rows of an image (w in the tile_scores layout)
-__device__ __forceinline__ void tile_accum(f32x4 (&o)[4], const AIM_LDS char* img, const f32x4 (&w)[4], int frow, int fq) {
+// tile_accum (attn_tile.h) with the transposed reads WRITTEN OUT, for win_attn_dkv_kernel alone: through tr_frag that kernel
+// takes 116 VGPRs where it took 112 (profiles/attn_tile_ab.md).  The rows, chunks and halves are those of aim_common.h tr_frag.
+__device__ __forceinline__ void tile_accum_dkv(f32x4 (&o)[4], const AIM_LDS char* img, const f32x4 (&w)[4], int frow, int fq) {
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
         bf16x8 pf;
@@ -154,10 +142,9 @@ __device__ __forceinline__ void tile_accum(f32x4 (&o)[4], const AIM_LDS char* im
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
             const int r0 = (2 * kk) * 16 + fq * 4 + (frow >> 2);
-            const int r1 = r0 + 16;
             const int ch = dt * 2 + ((frow & 3) >> 1), half = (frow & 1) * 8;
             const bf16x4 v0 = lds_read_tr4(img + swz_off(r0, ch) + half);
-            const bf16x4 v1 = lds_read_tr4(img + swz_off(r1, ch) + half);
+            const bf16x4 v1 = lds_read_tr4(img + swz_off(r0 + 16, ch) + half);
             bf16x8 vf;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -167,22 +154,6 @@ __device__ __forceinline__ void tile_accum(f32x4 (&o)[4], const AIM_LDS char* im
             o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf, o[dt], 0, 0, 0);
         }
     }
-}
-
-// the own token's 64 values: scale * o as bf16 at p[0 .. 63] (16-byte stores, tiles paired across 16-lane rows)
-__device__ __forceinline__ void store_own(bf16_t* p, const f32x4 (&o)[4], float scale, bool ok, int fq) {
-    bf16_t* op = p + ((fq & 1) ? 16 + (fq - 1) * 4 : fq * 4);
-#pragma unroll
-    for (int dt = 0; dt < 4; dt += 2) {
-        const bf16x8 v = pair_rows16(pack4(o[dt][0] * scale, o[dt][1] * scale, o[dt][2] * scale, o[dt][3] * scale),
-                                     pack4(o[dt + 1][0] * scale, o[dt + 1][1] * scale, o[dt + 1][2] * scale, o[dt + 1][3] * scale));
-        if (ok) *(bf16x8*)(op + dt * 16) = v;
-    }
-}
-
-__device__ __forceinline__ void load_frag(bf16x8 (&f)[2], const bf16_t* row, int fq) {
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) f[ks] = *(const bf16x8*)(row + (ks * 4 + fq) * 8);
 }
 
 #define WIN_PROLOGUE                                                                           \
@@ -258,7 +229,7 @@ __global__ __launch_bounds__(512) void win_attn_fwd_kernel(const bf16_t* __restr
     if (!active) return;
     const float inv = 1.0f / l;
     if (fq == 0 && own_ok) lse[stat_index(g, it, orow)] = m * 0.125f + __logf(l);
-    store_own(out + ((long long)it.b * clip_rows + orow) * D + it.h * 64, o, inv, own_ok, fq);
+    store_tiles16(out + ((long long)it.b * clip_rows + orow) * D + it.h * 64, o, inv, own_ok, fq);
 }
 
 // own = queries: delta and dQ
@@ -311,7 +282,7 @@ __global__ __launch_bounds__(512) void win_attn_dq_kernel(const bf16_t* __restri
         tile_accum(acc, sA, s, frow, fq);
     }
     if (!active) return;
-    store_own(dqkv + grow * ld + it.h * 64, acc, 1.0f, own_ok, fq);
+    store_tiles16(dqkv + grow * ld + it.h * 64, acc, 1.0f, own_ok, fq);
 }
 
 // own = keys: dK and dV
@@ -363,12 +334,12 @@ __global__ __launch_bounds__(512) void win_attn_dkv_kernel(const bf16_t* __restr
                 dp[t][e] = p * (dp[t][e] - d[e]) * 0.125f;
             }
         }
-        tile_accum(dv, sB, s, frow, fq);
-        tile_accum(dk, sA, dp, frow, fq);
+        tile_accum_dkv(dv, sB, s, frow, fq);
+        tile_accum_dkv(dk, sA, dp, frow, fq);
     }
     if (!active) return;
-    store_own(dqkv + grow * ld + D + it.h * 64, dk, 1.0f, own_ok, fq);
-    store_own(dqkv + grow * ld + 2 * D + it.h * 64, dv, 1.0f, own_ok, fq);
+    store_tiles16(dqkv + grow * ld + D + it.h * 64, dk, 1.0f, own_ok, fq);
+    store_tiles16(dqkv + grow * ld + 2 * D + it.h * 64, dv, 1.0f, own_ok, fq);
 }
 
 // argument checks shared by both entry points; fills the geometry, the grid and the block size
