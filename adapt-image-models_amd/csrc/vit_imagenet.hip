@@ -226,3 +226,187 @@ extern "C" int aim_layernorm_gb_bwd(const void* dy, int dy_is_bf16, int64_t lddy
     AIM_CHECK_LAUNCH("aim_layernorm_gb_bwd(finish)");
     return 0;
 }
+
+namespace {
+
+// ---- TimeSformer (reference timesformer.py:196-208): the full backward of the fused stem x = ln_pre([cls ; tok] + pos + temporal)
+// (aim_embed_ln / aim_embed_ln_f32), for a model whose stem trains ----
+// Stage 1, grid (N, T), four waves: the block owns token n of frame-time t and its waves walk the clips b = wave, wave + 4, ...
+// One wave per row: u is rebuilt as the forward builds it, xhat = (u - mean) rstd, the two row means come from wave shuffles,
+// du = rstd (gamma dx - mean_d(gamma dx) - xhat mean_d(gamma dx xhat)).  du goes to dtok (rows n >= 1) and into three register
+// sums: du, dx xhat, dx.  The block adds its four waves in wave order through LDS and writes one row of each to the workspace:
+//   S[n][t][D] (du) | Gg[n*T + t][D] (dx xhat) | Gb[n*T + t][D] (dx)      -- 3 N T D floats.
+// Stage 2 adds those rows in a fixed order (embed_ln_bwd_finish_kernel, ln_gb_finish_kernel).  No atomics anywhere.
+constexpr int EMB_MAXC = 8;  // float4 chunks per lane: D <= 8*4*64 = 2048, what aim_embed_ln takes.  (NC <= 4, D <= 1024, is every model
+                             // built here and fits the registers; the bf16 instance at NC = 8 spills 764 of them: correct, not fast)
+
+template <int NC, typename TX>      // TX: the type of dx, tok and dtok (bf16_t | float)
+__global__ __launch_bounds__(256) void embed_ln_bwd_rows_kernel(const TX* __restrict__ dx, const TX* __restrict__ tok,
+                                                                const float* __restrict__ cls, const float* __restrict__ pos,
+                                                                const float* __restrict__ tmp, const float* __restrict__ gamma,
+                                                                const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                                TX* __restrict__ dtok, float* __restrict__ part, int B, int T,
+                                                                int N, int D) {
+    __shared__ float red[3][NC * 256];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int n = blockIdx.x, t = blockIdx.y, nch = D >> 2;
+    f32x4 adu[NC], adg[NC], adb[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) adu[c] = adg[c] = adb[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int b = wave; b < B; b += 4) {
+        const long long bt = (long long)b * T + t, row = bt * N + n;
+        const float mu = mean[row], rs = rstd[row];
+        f32x4 g[NC], xh[NC];
+        float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            const int ch = lane + c * 64;
+            if (ch < nch) {
+                f32x4 v = n == 0 ? *(const f32x4*)(cls + ch * 4) : load4f(tok + (bt * (N - 1) + (n - 1)) * D + ch * 4);
+                v += *(const f32x4*)(pos + (long long)n * D + ch * 4);
+                v += *(const f32x4*)(tmp + (long long)t * D + ch * 4);
+                const f32x4 d = load4f(dx + row * D + ch * 4);
+                const f32x4 gm = *(const f32x4*)(gamma + ch * 4);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    xh[c][e] = (v[e] - mu) * rs;
+                    g[c][e] = d[e] * gm[e];
+                    s1 += g[c][e];
+                    s2 += g[c][e] * xh[c][e];
+                    adg[c][e] = fmaf(d[e], xh[c][e], adg[c][e]);
+                    adb[c][e] += d[e];
+                }
+            }
+        }
+        const float m1 = wave_sum(s1) / (float)D, m2 = wave_sum(s2) / (float)D;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            const int ch = lane + c * 64;
+            if (ch < nch) {
+                f32x4 du;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) du[e] = rs * (g[c][e] - m1 - xh[c][e] * m2);
+                adu[c] += du;
+                if (dtok && n > 0) {
+                    TX* dst = dtok + (bt * (N - 1) + (n - 1)) * D + ch * 4;
+                    if constexpr (sizeof(TX) == 4)
+                        *(f32x4*)dst = du;
+                    else
+                        *(bf16x4*)dst = pack4(du[0], du[1], du[2], du[3]);
+                }
+            }
+        }
+    }
+    // the four waves' sums meet in LDS and are added in wave order; one quantity at a time (NC = 8: 24 KB of LDS)
+    const long long NT = (long long)gridDim.x * gridDim.y, p = (long long)n * T + t;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        f32x4* acc = q == 0 ? adu : (q == 1 ? adg : adb);
+        if (q > 0) __syncthreads();
+        if (wave > 0) {
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                const int ch = lane + c * 64;
+                if (ch < nch) *(f32x4*)(&red[wave - 1][ch * 4]) = acc[c];
+            }
+        }
+        __syncthreads();
+        if (wave == 0) {
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                const int ch = lane + c * 64;
+                if (ch < nch) {
+                    f32x4 a = acc[c];
+                    for (int w = 0; w < 3; ++w) a += *(const f32x4*)(&red[w][ch * 4]);
+                    *(f32x4*)(part + (q * NT + p) * D + ch * 4) = a;
+                }
+            }
+        }
+    }
+}
+
+// grid ((D + 63) / 64, N + T), 64 columns x 4 row groups.  blockIdx.y = n < N: dpos[n] += sum_t S[n][t] (and dcls += the same sum
+// for n = 0: the same additions in the same order, so d(class_embedding)'s increment has the bits of d(positional_embedding)[0]'s);
+// blockIdx.y = N + t: dtemporal[t] += sum_n S[n][t].  Group g adds rows g, g + 4, ... in order, then the four groups in order.
+__global__ __launch_bounds__(256) void embed_ln_bwd_finish_kernel(const float* __restrict__ S, float* __restrict__ dcls,
+                                                                  float* __restrict__ dpos, float* __restrict__ dtemporal, int T,
+                                                                  int N, int D) {
+    __shared__ float red[4][64];
+    const int cl = threadIdx.x & 63, g = threadIdx.x >> 6;
+    const int c = blockIdx.x * 64 + cl;
+    const bool live = c < D;
+    const bool tokens = (int)blockIdx.y < N;                    // (uniform over the block)
+    const int n = (int)blockIdx.y, t = (int)blockIdx.y - N;
+    if (tokens ? (!dpos && !(dcls && n == 0)) : !dtemporal) return;
+    float a = 0.f;
+    if (live) {
+        if (tokens)
+            for (int k = g; k < T; k += 4) a += S[((long long)n * T + k) * D + c];
+        else
+            for (int k = g; k < N; k += 4) a += S[((long long)k * T + t) * D + c];
+    }
+    red[g][cl] = a;
+    __syncthreads();
+    if (g == 0 && live) {
+        const float s = (red[0][cl] + red[1][cl]) + (red[2][cl] + red[3][cl]);
+        if (tokens) {
+            if (dpos) dpos[(long long)n * D + c] += s;
+            if (dcls && n == 0) dcls[c] += s;
+        } else {
+            dtemporal[(long long)t * D + c] += s;
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int64_t aim_embed_ln_bwd_workspace_bytes(int B, int T, int N, int D) {
+    if (B <= 0 || T <= 0 || N <= 0 || D <= 0) return 0;
+    return (int64_t)3 * N * T * D * 4;
+}
+
+extern "C" int aim_embed_ln_bwd(const void* dx, int is_bf16, const void* tok, const float* cls, const float* pos,
+                                const float* temporal, const float* gamma, const float* mean, const float* rstd, void* dtok,
+                                float* dcls, float* dpos, float* dtemporal, float* dgamma, float* dbeta, int B, int T, int N, int D,
+                                float* workspace, int64_t workspace_bytes, void* stream) {
+    AIM_CHECK_ARG(B > 0 && T > 0 && N > 1 && D > 0 && (D % 4) == 0 && D <= EMB_MAXC * 256 && T <= 65535 &&
+                      (long long)N + T <= 65535 && (long long)N * T <= (1 << 24),
+                  "embed_ln_bwd: bad shape B=%d T=%d N=%d D=%d (D a multiple of 4, at most %d; N + T at most 65535)", B, T, N, D,
+                  EMB_MAXC * 256);
+    AIM_CHECK_ARG(dx && tok && cls && pos && temporal && gamma && mean && rstd, "embed_ln_bwd: null input pointer");
+    AIM_CHECK_ARG(dtok || dcls || dpos || dtemporal || dgamma || dbeta, "embed_ln_bwd: no output requested");
+    // rows are moved four elements at a time: 16 bytes of f32, 8 bytes of bf16
+    const uintptr_t am = is_bf16 ? 7 : 15;
+    AIM_CHECK_ARG((((uintptr_t)dx | (uintptr_t)tok | (uintptr_t)dtok) & am) == 0 &&
+                      (((uintptr_t)cls | (uintptr_t)pos | (uintptr_t)temporal | (uintptr_t)gamma | (uintptr_t)workspace) & 15) == 0 &&
+                      (((uintptr_t)mean | (uintptr_t)rstd | (uintptr_t)dcls | (uintptr_t)dpos | (uintptr_t)dtemporal |
+                        (uintptr_t)dgamma | (uintptr_t)dbeta) & 3) == 0,
+                  "embed_ln_bwd: misaligned pointer (dx / tok / dtok: %d bytes; cls / pos / temporal / gamma / workspace: 16)",
+                  (int)am + 1);
+    AIM_CHECK_ARG(workspace && workspace_bytes >= aim_embed_ln_bwd_workspace_bytes(B, T, N, D),
+                  "embed_ln_bwd: workspace of %lld bytes needed", (long long)aim_embed_ln_bwd_workspace_bytes(B, T, N, D));
+    hipStream_t st = (hipStream_t)stream;
+    const int P = N * T;
+#define AIM_ELB(NC)                                                                                                       \
+    if (is_bf16)                                                                                                          \
+        hipLaunchKernelGGL((embed_ln_bwd_rows_kernel<NC, bf16_t>), dim3(N, T), dim3(256), 0, st, (const bf16_t*)dx,         \
+                           (const bf16_t*)tok, cls, pos, temporal, gamma, mean, rstd, (bf16_t*)dtok, workspace, B, T, N, D); \
+    else                                                                                                                  \
+        hipLaunchKernelGGL((embed_ln_bwd_rows_kernel<NC, float>), dim3(N, T), dim3(256), 0, st, (const float*)dx,           \
+                           (const float*)tok, cls, pos, temporal, gamma, mean, rstd, (float*)dtok, workspace, B, T, N, D)
+    const int nc = (D + 255) / 256;
+    if (nc <= 1) AIM_ELB(1); else if (nc == 2) AIM_ELB(2); else if (nc == 3) AIM_ELB(3); else if (nc == 4) AIM_ELB(4); else AIM_ELB(8);
+#undef AIM_ELB
+    AIM_CHECK_LAUNCH("aim_embed_ln_bwd(rows)");
+    if (dcls || dpos || dtemporal) {
+        hipLaunchKernelGGL(embed_ln_bwd_finish_kernel, dim3((D + 63) / 64, N + T), dim3(256), 0, st, workspace, dcls, dpos,
+                           dtemporal, T, N, D);
+        AIM_CHECK_LAUNCH("aim_embed_ln_bwd(finish)");
+    }
+    if (dgamma || dbeta) {      // the slabs [P][D] (dx xhat) and [P][D] (dx) behind S, summed as aim_layernorm_gb_bwd sums its slabs
+        hipLaunchKernelGGL(ln_gb_finish_kernel, dim3((D + 63) / 64), dim3(1024), 0, st, workspace + (long long)P * D, dgamma,
+                           dbeta, P, D);
+        AIM_CHECK_LAUNCH("aim_embed_ln_bwd(gamma, beta)");
+    }
+    return 0;
+}

@@ -139,9 +139,11 @@ SIGNATURES = {
     "aim_embed_nopre_bwd": [P, I, P, P, P, P, P, I, I, I, I, P, L, P],
     "aim_layernorm_gb_bwd_workspace_bytes": [I, I],
     "aim_layernorm_gb_bwd": [P, I, L, P, L, P, P, P, P, I, I, P, L, P],
+    "aim_embed_ln_bwd_workspace_bytes": [I, I, I, I],
+    "aim_embed_ln_bwd": [P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P, L, P],
 }
 
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 
 def load_library():

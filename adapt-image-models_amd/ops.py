@@ -702,6 +702,31 @@ def embed_bwd(dx, tok, cls, pos, temporal, gamma, mean, rstd, dtemporal, B, T, N
                             dtemporal.data_ptr(), B, T, N, D, ws.data_ptr(), nbytes, _stream()), "aim_embed_bwd")
 
 
+def embed_ln_bwd(dx, tok, cls, pos, temporal, gamma, mean, rstd, B, T, N, D, *, dtok=None, dcls=None, dpos=None, dtemporal=None,
+                 dgamma=None, dbeta=None):
+    """Full backward of ``embed_ln`` / ``embed_ln_f32`` from dx [B*T*N, D]: WRITES dtok [B*T*(N-1), D] (the token rows of
+    d(ln_pre's input)) and ADDS into dcls [D], dpos [N, D], dtemporal [T, D], dgamma [D], dbeta [D] (fp32); any output may be
+    None.  dx, tok and dtok share one dtype: bf16 (the bf16 path) or f32.  Two ordered stages (reproducible, no atomics)."""
+    _chk(dx, dx.dtype if dx.dtype in (F32, BF16) else F32, "dx")
+    _chk(tok, dx.dtype, "tok"); _chk(dtok, dx.dtype, "dtok")
+    for n_, t_ in (("cls", cls), ("pos", pos), ("temporal", temporal), ("gamma", gamma), ("mean", mean), ("rstd", rstd),
+                   ("dcls", dcls), ("dpos", dpos), ("dtemporal", dtemporal), ("dgamma", dgamma), ("dbeta", dbeta)):
+        _chk(t_, F32, n_)
+    sizes = dict(dx=(dx, B * T * N * D), tok=(tok, B * T * (N - 1) * D), cls=(cls, D), pos=(pos, N * D), temporal=(temporal, T * D),
+                 gamma=(gamma, D), mean=(mean, B * T * N), rstd=(rstd, B * T * N), dtok=(dtok, B * T * (N - 1) * D), dcls=(dcls, D),
+                 dpos=(dpos, N * D), dtemporal=(dtemporal, T * D), dgamma=(dgamma, D), dbeta=(dbeta, D))
+    for n_, (t_, numel) in sizes.items():
+        if t_ is not None and (not t_.is_contiguous() or t_.numel() != numel):
+            raise ValueError(f"embed_ln_bwd: {n_} must be contiguous with {numel} elements, got {tuple(t_.shape)}")
+    lib = load_library()
+    nbytes = lib.aim_embed_ln_bwd_workspace_bytes(B, T, N, D)
+    ws = torch.empty((max(nbytes, 16) // 4,), dtype=F32, device=dx.device)
+    check(lib.aim_embed_ln_bwd(dx.data_ptr(), int(dx.dtype == BF16), tok.data_ptr(), cls.data_ptr(), pos.data_ptr(),
+                               temporal.data_ptr(), gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _p(dtok), _p(dcls), _p(dpos),
+                               _p(dtemporal), _p(dgamma), _p(dbeta), B, T, N, D, ws.data_ptr(), nbytes, _stream()),
+          "aim_embed_ln_bwd")
+
+
 def embed_nopre_fwd(tok, cls, pos, temporal, x, B, T, N, D):
     """ViT_ImageNet embedding (no ln_pre): x [B*T*N, D] = ((cls | tok) + pos) + temporal; tok f32 [B*T*(N-1), D] (conv + bias)."""
     for n_, t_ in (("tok", tok), ("cls", cls), ("pos", pos), ("temporal", temporal), ("x", x)):

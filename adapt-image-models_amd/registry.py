@@ -145,6 +145,8 @@ def register_into_mmaction() -> bool:
     MB.register_module(name="AIM_FLASH", force=True, module=AIM_FLASH)             # vitclip_aim_flash.py:402, wind_attn=True
     from .zeroi2v import ViT_CLIP_ZEROI2V
     MB.register_module(name="ViT_CLIP_ZEROI2V", force=True, module=ViT_CLIP_ZEROI2V)       # vit_clip_zeroI2V.py:361
+    from .timesformer import TimeSformer
+    MB.register_module(name="TimeSformer", force=True, module=TimeSformer)                 # timesformer.py:86
     return True
 
 

@@ -32,7 +32,7 @@ extern "C" {
 
 typedef uint16_t aim_bf16;
 
-#define AIM_ABI_VERSION 16
+#define AIM_ABI_VERSION 17
 
 int aim_version(void);                /* == AIM_ABI_VERSION */
 const char* aim_last_error(void);     /* message of the last failing call on this thread */
@@ -607,6 +607,26 @@ int64_t aim_layernorm_gb_bwd_workspace_bytes(int rows, int D);
 int aim_layernorm_gb_bwd(const void* dy, int dy_is_bf16, int64_t lddy, const float* x, int64_t ldx, const float* mean,
                          const float* rstd, float* dgamma, float* dbeta, int rows, int D, float* workspace,
                          int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * TimeSformer (reference timesformer.py; ABI 17): the FULL backward of the fused stem aim_embed_ln / aim_embed_ln_f32,
+ * x = ln_pre(u), u[bt*N + n] = ((n == 0 ? cls : tok[bt*(N-1) + n-1]) + pos[n]) + temporal[t], for a model whose stem trains
+ * (aim_embed_bwd gives d temporal only).  With xhat = (u - mean) rstd and g = gamma dx per row:
+ *   du = rstd (g - mean_d(g) - xhat mean_d(g xhat));  dtok = rows n >= 1 of du, WRITTEN;
+ *   dcls += sum_bt du[bt, 0]; dpos[n] += sum_bt du[bt, n]; dtemporal[t] += sum_{b, n} du[b*T + t, n];
+ *   dgamma += sum_rows dx xhat; dbeta += sum_rows dx        (all five f32, ADDED into).
+ * is_bf16 != 0: dx, tok and dtok are bf16 (the bf16 path); 0: all three f32.  Every output is optional (NULL: untouched); all
+ * six NULL is refused.  fp32 arithmetic, one wave per row.  Two ordered stages through the workspace (3 N T D floats: one
+ * partial row per (token, frame-time) and quantity, then fixed-order sums over them): no atomics, equal bits on every run, and
+ * dcls's increment has the bits of dpos[0]'s.  Refused before any launch: D not a multiple of 4 or above 2048, N < 2,
+ * N + T > 65535, a short workspace, dx / tok / dtok not aligned to four elements, cls / pos / temporal / gamma / workspace
+ * not 16-byte aligned.
+ * ------------------------------------------------------------------------------------------ */
+int64_t aim_embed_ln_bwd_workspace_bytes(int B, int T, int N, int D);
+int aim_embed_ln_bwd(const void* dx, int is_bf16, const void* tok, const float* cls, const float* pos, const float* temporal,
+                     const float* gamma, const float* mean, const float* rstd, void* dtok, float* dcls, float* dpos,
+                     float* dtemporal, float* dgamma, float* dbeta, int B, int T, int N, int D, float* workspace,
+                     int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
