@@ -856,14 +856,14 @@ def _embed_forward(model, frozen, imgs, temporal):
     return tok, x0, mean0, rstd0, tmp
 
 
-def _ln_post_forward(x, lnp_w, lnp_b, BT, P):
+def _ln_post_forward(x, lnp_w, lnp_b, BT, P, eps: float = 1e-5):
     """ln_post on the class rows only (LayerNorm is per-row; vit_clip.py:452-453): row 0 of every frame of an fp32 stream with
     P rows per frame.  Returns (y [BT, D] f32, gw, meanp, rstdp)."""
     D, dev = x.shape[1], x.device
     gw, gb = lnp_w.detach().float().contiguous(), lnp_b.detach().float().contiguous()
     y = _empty((BT, D), F32, dev)
     meanp, rstdp = _empty((BT,), F32, dev), _empty((BT,), F32, dev)
-    ops.layernorm_fwd(x, gw, gb, BT, D, P * D, y_f32=y, mean=meanp, rstd=rstdp)
+    ops.layernorm_fwd(x, gw, gb, BT, D, P * D, y_f32=y, mean=meanp, rstd=rstdp, eps=eps)
     return y, gw, meanp, rstdp
 
 

@@ -23,7 +23,6 @@ gathered again.  A parameter whose ``requires_grad`` is False gets ``None`` and 
 reproducible.  ``set_precision('fp32')`` runs the same forward and backward on the fp32 kernels (timesformer_fp32.py), reading a
 block through the same ``_block_view``.
 """
-import logging
 from collections import OrderedDict
 from typing import Dict, List, Optional
 
@@ -31,10 +30,9 @@ import torch
 from torch import nn
 
 from . import ops
-from .backbone import BF16, F32, _AUX_GRAD, LayerNorm, QuickGELU, _cast, _conv_operand, _empty
+from .backbone import BF16, F32, _AUX_GRAD, LayerNorm, QuickGELU, _cast, _conv_operand, _empty, _ln_post_forward
+from .full_param import FullParamBackbone, GradBufs, conv_wgrad, ln_post_backward
 from .registry import BACKBONES
-
-_LOG = logging.getLogger("aim_amd")
 
 # the seven Linear layers of a block, in the order the backward meets them last to first
 _LINEARS = ("t_qkv", "t_out", "t_ad", "qkv", "out", "fc", "pr")
@@ -271,11 +269,7 @@ class _TimeSformerFn(torch.autograd.Function):
         for i in range(L):
             x, c = _block_forward(x, ops_["blocks"][i], B, T, N, H, *factors[i], need_grad)
             ctxs.append(c)
-        gw = P["ln_post.weight"].detach().float().contiguous()
-        gb = P["ln_post.bias"].detach().float().contiguous()
-        y = _empty((BT, D), F32, dev)
-        meanp, rstdp = _empty((BT,), F32, dev), _empty((BT,), F32, dev)
-        ops.layernorm_fwd(x, gw, gb, BT, D, N * D, y_f32=y, mean=meanp, rstd=rstdp)
+        y, gw, meanp, rstdp = _ln_post_forward(x, P["ln_post.weight"], P["ln_post.bias"], BT, N)
         if need_grad:
             ctx.model, ctx.dims, ctx.need = model, (B, T, N, H, D, L, G), need
             ctx.saved = dict(ctxs=ctxs, ops=ops_, xL=x, gw=gw, meanp=meanp, rstdp=rstdp, imgs=imgs, params=params, tok=tok,
@@ -287,28 +281,15 @@ class _TimeSformerFn(torch.autograd.Function):
         model = ctx.model
         B, T, N, H, D, L, G = ctx.dims
         s, need = ctx.saved, ctx.need
-        BT, M = B * T, B * T * N
+        BT = B * T
         dev = dout.device
-        params = s["params"]
-        names = model._param_names()
-        # every kernel ACCUMULATES into these; with `grad_in_place` (dist.build_optimizer's flat-buffer optimizer) they are the
-        # existing `param.grad` views of the flat gradient buffer and autograd gets None for them
-        in_place = [bool(need[k] and model.grad_in_place and p_.grad is not None and p_.grad.dtype == F32
-                         and p_.grad.is_contiguous() and p_.grad.device == dev) for k, p_ in enumerate(params)]
-        grads = [p_.grad if in_place[k] else (torch.zeros_like(p_, dtype=F32) if need[k] else None)
-                 for k, p_ in enumerate(params)]
-        G_ = dict(zip(names, grads))
-        dy = dout.permute(0, 2, 1).reshape(BT, D).contiguous().float()
-        dxb = torch.zeros((M, D), dtype=BF16, device=dev)
-        ops.layernorm_bwd(dy, s["xL"], s["gw"], s["meanp"], s["rstdp"], BT, D, lddy=D, ldx=N * D, lddx=N * D, dx_bf16=dxb)
-        if G_["ln_post.weight"] is not None or G_["ln_post.bias"] is not None:
-            ops.layernorm_gb_bwd(dy, s["xL"], s["meanp"], s["rstdp"], BT, D, G_["ln_post.weight"], G_["ln_post.bias"],
-                                 ldx=N * D)
+        # every kernel ACCUMULATES into these; with `grad_in_place` they are the `param.grad` views of the flat gradient buffer
+        G_ = GradBufs(model._param_names(), s["params"], need, dev, model.grad_in_place)
+        dxb = ln_post_backward(dout, s, G_["ln_post.weight"], G_["ln_post.bias"], BT, N, BF16)
         s["xL"] = None
         eye = model._identity(dev)
         for i in reversed(range(L)):
-            pre = f"transformer.resblocks.{i}."
-            gr = {n[len(pre):]: t for n, t in G_.items() if n.startswith(pre) and t is not None}
+            gr = G_.block(f"transformer.resblocks.{i}.")
             dxb = _block_backward(dxb, s["ctxs"][i], s["ops"]["blocks"][i], gr, eye, B, T, N, H)
             s["ctxs"][i] = None
         # the stem: ln_pre, the three embeddings, and the token rows of d(ln_pre's input) for the conv weight
@@ -321,22 +302,10 @@ class _TimeSformerFn(torch.autograd.Function):
                              dtok=dtok, dcls=gcls, dpos=gpos, dtemporal=None if gtmp is None else gtmp.view(T, D), dgamma=ggam,
                              dbeta=gbet)
         del dxb
-        if gconv is not None:        # the patch matrix was freed after the forward's GEMM: gather it again
-            imgs = s["imgs"]
-            p = model.patch_size
-            Kp, K = s["ops"]["conv"].shape[1], 3 * p * p
-            A = _empty((BT * (N - 1), Kp), BF16, dev)
-            ops.patchify(imgs, A, B, T, imgs.shape[3], imgs.shape[4], p, Kp)
-            dwc = torch.zeros((D, Kp), dtype=F32, device=dev) if Kp != K else gconv.view(D, K)
-            ops.wgrad(dtok, A, dwc)
-            if Kp != K:
-                gconv.view(D, K).add_(dwc[:, :K])
+        if gconv is not None:
+            conv_wgrad(s["imgs"], dtok, gconv, model.patch_size, s["ops"]["conv"].shape[1])
         ctx.saved = None
-        out = []
-        for k, p_ in enumerate(params):
-            gk = None if in_place[k] else grads[k]
-            out.append(gk if gk is None or gk.dtype == p_.dtype else gk.to(p_.dtype))
-        return (None, None, None) + tuple(out)
+        return G_.result(3)
 
 
 def clip_state_dict(visual_sd: Dict[str, torch.Tensor], model: "TimeSformer") -> "OrderedDict[str, torch.Tensor]":
@@ -361,7 +330,7 @@ def clip_state_dict(visual_sd: Dict[str, torch.Tensor], model: "TimeSformer") ->
 
 
 @BACKBONES.register_module()
-class TimeSformer(nn.Module):
+class TimeSformer(FullParamBackbone):
     """Full fine-tuning on the CLIP-layout ViT (reference timesformer.py:86-225); constructor keywords and defaults of the
     reference."""
 
@@ -390,34 +359,15 @@ class TimeSformer(nn.Module):
             self.temporal_embedding = nn.Parameter(torch.zeros(1, num_frames, width))
         self.transformer = Transformer(num_frames, width, layers, heads, scale=adapter_scale, drop_path=drop_path_rate)
         self.ln_post = LayerNorm(width)
-        self._operand_cache = None
         self._eye = None
-        self._names_cache = None
-        self.weights_epoch = 0                      # bumped by an attached dist.FlatAdamW's step(): weights changed in place
-        self.grad_in_place = False                  # accumulate straight into param.grad (set by dist.build_optimizer)
         self.grad_ready_hook = None                 # set by dist.FlatAdamW and never called: gradients are reduced after the backward
-        self.inference_precision = 'bf16'
-        self.precision = 'bf16'
-        self._fp8_warned = False
 
     # ---- reference API ------------------------------------------------------------------------
     def init_weights(self, pretrained=None):
         """Reference ``init_weights`` (:117-182): trunc_normal_(.02) Linear weights, zero biases, LayerNorms 1 / 0, optional
         CLIP load.  Nothing is frozen, and nothing is zeroed: the reference's zeroing loops look for a ``D_fc2`` child, which
         the plain-Linear ``T_Adapter`` does not have."""
-        def _init_weights(m):
-            if isinstance(m, nn.Linear):
-                nn.init.trunc_normal_(m.weight, std=.02)
-                if m.bias is not None:
-                    nn.init.constant_(m.bias, 0)
-            elif isinstance(m, nn.LayerNorm):
-                nn.init.constant_(m.bias, 0)
-                nn.init.constant_(m.weight, 1.0)
-
-        if pretrained:
-            self.pretrained = pretrained
-        if isinstance(self.pretrained, str):
-            self.apply(_init_weights)
+        if self._init_then_wants_load(pretrained):
             try:
                 import clip  # noqa: F401
             except ImportError as e:
@@ -430,11 +380,6 @@ class TimeSformer(nn.Module):
             sd = clip_model.visual.state_dict()
             del clip_model
             self.load_state_dict(clip_state_dict(sd, self), strict=True)
-        elif self.pretrained is None:
-            self.apply(_init_weights)
-        else:
-            raise TypeError('pretrained must be a str or None')
-        self._operand_cache = None
 
     @torch.jit.ignore
     def no_weight_decay(self):
@@ -444,44 +389,18 @@ class TimeSformer(nn.Module):
     def no_weight_decay_keywords(self):
         return {'relative_position_bias_table', 'temporal_position_bias_table'}
 
-    def set_precision(self, precision: str):
-        """'bf16' (default) | 'fp32': the reference-precision verification mode (timesformer_fp32.py: f32-MFMA kernels, the
-        same hand-written backward in fp32, plain autograd outputs)."""
-        if precision not in ('bf16', 'fp32'):
-            raise ValueError("precision must be 'bf16' or 'fp32'")
-        self.precision = precision
-        return self
-
-    def set_inference_precision(self, precision: str):
-        """'bf16' | 'fp8'; TimeSformer has no fp8 path: 'fp8' warns once and runs bf16."""
-        if precision not in ('bf16', 'fp8'):
-            raise ValueError("inference precision must be 'bf16' or 'fp8'")
-        self.inference_precision = precision
-        return self
-
     # ---- operand staging ------------------------------------------------------------------------
-    def _param_names(self):
-        if self._names_cache is None:
-            self._names_cache = [n for n, _ in self.named_parameters()]
-        return self._names_cache
-
     def _operands(self):
-        """bf16 copies of the GEMM weights (and fp32 copies of the small tensors the kernels read); rebuilt when one of them
-        changed: moved, changed version, or -- when any of them trains -- an optimizer step that wrote them through raw pointers
-        (``FlatAdamW.generation``, ``weights_epoch``)."""
-        from .dist import FlatAdamW
+        """bf16 copies of the GEMM weights (and fp32 copies of the small tensors the kernels read), cached across forwards
+        (``_cached_operands``)"""
         ps = [p for n, p in self.named_parameters() if n not in ("temporal_embedding", "ln_pre.weight", "ln_pre.bias",
                                                                   "ln_post.weight", "ln_post.bias")]
-        key = tuple((p.data_ptr(), p._version) for p in ps)
-        if any(p.requires_grad for p in ps):     # (a FlatAdamW step writes through raw pointers: no version changes)
-            key += (self.weights_epoch, FlatAdamW.generation)
-        if self._operand_cache is not None and self._operand_cache[0] == key:
-            return self._operand_cache[1]
+        return self._cached_operands(ps, self._build_operands)
+
+    def _build_operands(self):
         f = lambda t: t.detach().float().contiguous()
-        out = dict(conv=_conv_operand(self.conv1.weight), cls=f(self.class_embedding), pos=f(self.positional_embedding),
-                   blocks=[_BlockW(_block_view(blk)) for blk in self.transformer.resblocks])
-        self._operand_cache = (key, out)
-        return out
+        return dict(conv=_conv_operand(self.conv1.weight), cls=f(self.class_embedding), pos=f(self.positional_embedding),
+                    blocks=[_BlockW(_block_view(blk)) for blk in self.transformer.resblocks])
 
     def _identity(self, dev):
         """the bf16 [D, D] identity behind the one row-scaling GEMM of a block's backward (``_block_backward``)"""
@@ -521,29 +440,6 @@ class TimeSformer(nn.Module):
 
     # ---- forward --------------------------------------------------------------------------------
     def forward(self, x: torch.Tensor):
-        if not x.is_cuda:
-            raise RuntimeError("aim_amd.TimeSformer runs on MI355X only (HIP kernels); there is no CPU fallback")
-        B, C, T, H, W = x.shape
-        if T != self.num_frames:
-            raise ValueError(f"expected {self.num_frames} frames, got {T}")
-        if C != 3 or H != self.input_resolution or W != self.input_resolution:
-            raise ValueError(f"expected input [B,3,{T},{self.input_resolution},{self.input_resolution}], got {tuple(x.shape)}")
-        if x.dtype not in (torch.float32, torch.float16, torch.bfloat16):
-            raise TypeError(f"TimeSformer takes float clips, got {x.dtype}")
-        if x.dtype == torch.float16:
-            x = x.float()
-        x = x.contiguous()
-        if self.inference_precision == 'fp8' and not self._fp8_warned:
-            self._fp8_warned = True
-            _LOG.warning("fp8 inference was requested but TimeSformer has no fp8 path: this forward runs bf16")
-        params = [p for _, p in self.named_parameters()]
-        if self.precision == 'fp32':
-            from .timesformer_fp32 import _TimeSformerFn32, forward_f32
-            if torch.is_grad_enabled() and any(p.requires_grad for p in params):
-                y = _TimeSformerFn32.apply(self, x, *params)
-            else:
-                with torch.no_grad():
-                    y = forward_f32(self, x, dict(zip(self._param_names(), params)), ())[0]
-            return y.unsqueeze(-1).unsqueeze(-1)
-        y = _TimeSformerFn.apply(self, torch.is_grad_enabled(), x, *params)      # [B, D, T]
-        return y.unsqueeze(-1).unsqueeze(-1)
+        x = self._check_clip(x, self.input_resolution)
+        from .timesformer_fp32 import _TimeSformerFn32, forward_f32
+        return self._dispatch(x, _TimeSformerFn, _TimeSformerFn32, forward_f32)

@@ -16,7 +16,9 @@ mode, not a fast path (the f32 MFMA runs at 1/16 of the bf16 rate).
 import torch
 
 from . import ops
+from .backbone import _ln_post_forward
 from .fp32_path import _e, _f
+from .full_param import GradBufs, conv_wgrad_f32, ln_post_backward, node_forward_f32
 from .timesformer import _NAMES, _STEM, _block_view
 
 F32 = torch.float32
@@ -194,10 +196,7 @@ def forward_f32(model, imgs, P, wants):
         x, c = block_forward_f32(x, w, B, T, N, H, *factors[i], save)
         ctxs.append(c)
         blocks.append(w if save else None)
-    gw = _f(P["ln_post.weight"])
-    y = _e((BT, D), dev)
-    meanp, rstdp = _e((BT,), dev), _e((BT,), dev)
-    ops.layernorm_fwd(x, gw, _f(P["ln_post.bias"]), BT, D, N * D, y_f32=y, mean=meanp, rstd=rstdp)
+    y, gw, meanp, rstdp = _ln_post_forward(x, P["ln_post.weight"], P["ln_post.bias"], BT, N)
     y = y.reshape(B, T, D).permute(0, 2, 1)
     saved = dict(ctxs=ctxs, blocks=blocks, xL=x, gw=gw, meanp=meanp, rstdp=rstdp, imgs=imgs, tok=tok, cls=cls, pos=pos, tmp=tmp,
                  gpre=gpre, mean0=mean0, rstd0=rstd0, dims=(B, T, N, H, D, L, G)) if save else None
@@ -210,30 +209,18 @@ class _TimeSformerFn32(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, model, imgs, *params):
-        names = model._param_names()
-        ctx.need = [bool(ctx.needs_input_grad[2 + k]) for k in range(len(params))]
-        y, saved = forward_f32(model, imgs, dict(zip(names, params)), {n for n, nd in zip(names, ctx.need) if nd})
-        ctx.model, ctx.saved, ctx.params = model, saved, params
-        return y
+        return node_forward_f32(ctx, forward_f32, model, imgs, params)
 
     @staticmethod
     def backward(ctx, dout):
-        model, s, params, need = ctx.model, ctx.saved, ctx.params, ctx.need
+        model, s = ctx.model, ctx.saved
         B, T, N, H, D, L, G = s["dims"]
-        BT, M = B * T, B * T * N
+        BT = B * T
         dev = dout.device
-        names = model._param_names()
-        grads = [torch.zeros(p_.shape, dtype=F32, device=dev) if nd else None for p_, nd in zip(params, need)]
-        GR = dict(zip(names, grads))
-        dy = dout.permute(0, 2, 1).reshape(BT, D).contiguous().float()
-        dx = torch.zeros((M, D), dtype=F32, device=dev)
-        ops.layernorm_bwd(dy, s["xL"], s["gw"], s["meanp"], s["rstdp"], BT, D, lddy=D, ldx=N * D, lddx=N * D, dx=dx)
-        if GR["ln_post.weight"] is not None or GR["ln_post.bias"] is not None:
-            ops.layernorm_gb_bwd(dy, s["xL"], s["meanp"], s["rstdp"], BT, D, GR["ln_post.weight"], GR["ln_post.bias"], ldx=N * D)
+        GR = GradBufs(model._param_names(), ctx.params, ctx.need, dev, False)      # (this mode never accumulates in place)
+        dx = ln_post_backward(dout, s, GR["ln_post.weight"], GR["ln_post.bias"], BT, N, F32)
         for i in reversed(range(L)):
-            pre = f"transformer.resblocks.{i}."
-            gi = {n[len(pre):]: t for n, t in GR.items() if n.startswith(pre) and t is not None}
-            dx = block_backward_f32(dx, s["ctxs"][i], s["blocks"][i], gi, B, T, N, H)
+            dx = block_backward_f32(dx, s["ctxs"][i], s["blocks"][i], GR.block(f"transformer.resblocks.{i}."), B, T, N, H)
             s["ctxs"][i] = s["blocks"][i] = None
         gconv = GR["conv1.weight"]
         dtok = _e((BT * (N - 1), D), dev) if gconv is not None else None
@@ -244,11 +231,6 @@ class _TimeSformerFn32(torch.autograd.Function):
                              dcls=gcls, dpos=gpos, dtemporal=None if gtmp is None else gtmp.view(T, D), dgamma=ggam, dbeta=gbet)
         del dx
         if gconv is not None:
-            p, imgs = model.patch_size, s["imgs"]
-            K = 3 * p * p
-            A = _e((BT * (N - 1), K), dev)
-            ops.patchify(imgs, A, B, T, imgs.shape[3], imgs.shape[4], p, K)
-            ops.wgrad_f32(dtok, A, gconv.view(D, K))
+            conv_wgrad_f32(s["imgs"], dtok, gconv, model.patch_size)
         ctx.saved = None
-        out = [None if g_ is None else (g_ if g_.dtype == p_.dtype else g_.to(p_.dtype)) for g_, p_ in zip(grads, params)]
-        return (None, None) + tuple(out)
+        return GR.result(2)

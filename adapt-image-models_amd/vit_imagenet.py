@@ -29,7 +29,8 @@ from torch import nn
 
 from . import ops
 from .backbone import (BF16, F32, _AUX_FRAG, _AUX_GRAD, _SMALL_ADAPTERS as _SMALL, _AdapterW, _Frozen, _clip_names, _conv_operand,
-                       _empty)
+                       _empty, _ln_post_forward)
+from .full_param import FullParamBackbone, GradBufs, conv_wgrad, ln_post_backward
 from .registry import BACKBONES
 
 _LOG = logging.getLogger("aim_amd")
@@ -329,11 +330,7 @@ class _ViTImageNetFn(torch.autograd.Function):
             keep = dict(qkv=wants[pre + "attn.qkv.weight"], proj=wants[pre + "attn.proj.weight"])
             x, c = _block_forward(x, ops_["blocks"][i], adp[i], B, T, N, H, masks[i, 0], masks[i, 1], need_grad, keep)
             ctxs.append(c)
-        gw = P["ln_post.weight"].detach().float().contiguous()
-        gb = P["ln_post.bias"].detach().float().contiguous()
-        y = _empty((BT, D), F32, dev)
-        meanp, rstdp = _empty((BT,), F32, dev), _empty((BT,), F32, dev)
-        ops.layernorm_fwd(x, gw, gb, BT, D, N * D, y_f32=y, mean=meanp, rstd=rstdp, eps=model.eps)
+        y, gw, meanp, rstdp = _ln_post_forward(x, P["ln_post.weight"], P["ln_post.bias"], BT, N, eps=model.eps)
         if need_grad:
             ctx.model, ctx.dims, ctx.need = model, (B, T, N, H, D, L, G), need
             ctx.saved = dict(ctxs=ctxs, adp=adp, ops=ops_, xL=x, gw=gw, meanp=meanp, rstdp=rstdp, imgs=imgs, params=params)
@@ -344,29 +341,14 @@ class _ViTImageNetFn(torch.autograd.Function):
         model = ctx.model
         B, T, N, H, D, L, G = ctx.dims
         s, need = ctx.saved, ctx.need
-        BT, M = B * T, B * T * N
+        BT = B * T
         dev = dout.device
-        params = s["params"]
-        names = model._param_names()
-        # every kernel ACCUMULATES into these; with `grad_in_place` (dist.build_optimizer's flat-buffer optimizer) they are the
-        # existing `param.grad` views of the flat gradient buffer and autograd gets None for them: no zero-filled temporaries
-        # and no second pass to add them into the buffer
-        in_place = [bool(need[k] and model.grad_in_place and p_.grad is not None and p_.grad.dtype == F32
-                         and p_.grad.is_contiguous() and p_.grad.device == dev) for k, p_ in enumerate(params)]
-        grads = [p_.grad if in_place[k] else (torch.zeros_like(p_, dtype=F32) if need[k] else None)
-                 for k, p_ in enumerate(params)]
-        G_ = dict(zip(names, grads))
-        dy = dout.permute(0, 2, 1).reshape(BT, D).contiguous().float()
-        dxb = torch.zeros((M, D), dtype=BF16, device=dev)
-        ops.layernorm_bwd(dy, s["xL"], s["gw"], s["meanp"], s["rstdp"], BT, D, lddy=D, ldx=N * D, lddx=N * D, dx_bf16=dxb)
-        if G_["ln_post.weight"] is not None or G_["ln_post.bias"] is not None:
-            ops.layernorm_gb_bwd(dy, s["xL"], s["meanp"], s["rstdp"], BT, D, G_["ln_post.weight"], G_["ln_post.bias"],
-                                 ldx=N * D)
+        # every kernel ACCUMULATES into these; with `grad_in_place` they are the `param.grad` views of the flat gradient buffer
+        G_ = GradBufs(model._param_names(), s["params"], need, dev, model.grad_in_place)
+        dxb = ln_post_backward(dout, s, G_["ln_post.weight"], G_["ln_post.bias"], BT, N, BF16)
         s["xL"] = None
         for i in reversed(range(L)):
-            pre = f"blocks.{i}."
-            gr = {n[len(pre):]: t for n, t in G_.items() if n.startswith(pre) and t is not None}
-            dxb = _block_backward(dxb, s["ctxs"][i], s["ops"]["blocks"][i], s["adp"][i], gr, B, T, N, H)
+            dxb = _block_backward(dxb, s["ctxs"][i], s["ops"]["blocks"][i], s["adp"][i], G_.block(f"blocks.{i}."), B, T, N, H)
             s["ctxs"][i] = None
         # embedding: cls_token / pos_embed / temporal_embedding / conv bias, and the token rows of d(x) for the conv weight
         gconv = G_["patch_embed.proj.weight"]
@@ -378,22 +360,10 @@ class _ViTImageNetFn(torch.autograd.Function):
                             dtemporal=None if gtmp is None else gtmp.view(T, D),
                             dbias=G_.get("patch_embed.proj.bias"))
         del dxb
-        if gconv is not None:        # the patch matrix was freed after the forward's GEMM: gather it again
-            imgs = s["imgs"]
-            p = model.patch_size
-            Kp, K = s["ops"]["conv"].shape[1], 3 * p * p
-            A = _empty((BT * (N - 1), Kp), BF16, dev)
-            ops.patchify(imgs, A, B, T, imgs.shape[3], imgs.shape[4], p, Kp)
-            dwc = torch.zeros((D, Kp), dtype=F32, device=dev) if Kp != K else gconv.view(D, K)
-            ops.wgrad(dtok, A, dwc)
-            if Kp != K:
-                gconv.view(D, K).add_(dwc[:, :K])
+        if gconv is not None:
+            conv_wgrad(s["imgs"], dtok, gconv, model.patch_size, s["ops"]["conv"].shape[1])
         ctx.saved = None
-        out = []
-        for k, p_ in enumerate(params):
-            gk = None if in_place[k] else grads[k]
-            out.append(gk if gk is None or gk.dtype == p_.dtype else gk.to(p_.dtype))
-        return (None, None, None) + tuple(out)
+        return G_.result(3)
 
 
 def _layernorm_eps(norm_layer) -> float:
@@ -407,7 +377,7 @@ def _layernorm_eps(norm_layer) -> float:
 
 
 @BACKBONES.register_module()
-class ViT_ImageNet(nn.Module):
+class ViT_ImageNet(FullParamBackbone):
     """AIM on an ImageNet-21k ViT (reference vit_imagenet.py:129-266); constructor keywords and defaults of the reference."""
 
     def __init__(self, img_size=224, num_frames=8, patch_size=16, in_chans=3, embed_dim=768, depth=12, adapter_scale=0.5,
@@ -445,31 +415,13 @@ class ViT_ImageNet(nn.Module):
         self.ln_post = nn.LayerNorm(embed_dim, eps=eps)
         nn.init.trunc_normal_(self.pos_embed, std=.02)
         nn.init.trunc_normal_(self.cls_token, std=.02)
-        self._frozen_cache = None
         self._cast_table = None
-        self.weights_epoch = 0                      # bumped by an attached dist.FlatAdamW's step(): weights changed in place
-        self.grad_in_place = False                  # accumulate straight into param.grad (set by dist.build_optimizer)
-        self.inference_precision = 'bf16'
-        self.precision = 'bf16'
-        self._fp8_warned = False
 
     # ---- reference API ------------------------------------------------------------------------
     def init_weights(self, pretrained=None):
         """Reference ``init_weights`` (:180-236): init, optional load of the local jx ViT-B/16 checkpoint, zero every adapter's
         D_fc2.  Nothing is frozen."""
-        def _init_weights(m):
-            if isinstance(m, nn.Linear):
-                nn.init.trunc_normal_(m.weight, std=.02)
-                if m.bias is not None:
-                    nn.init.constant_(m.bias, 0)
-            elif isinstance(m, nn.LayerNorm):
-                nn.init.constant_(m.bias, 0)
-                nn.init.constant_(m.weight, 1.0)
-
-        if pretrained:
-            self.pretrained = pretrained
-        if isinstance(self.pretrained, str):
-            self.apply(_init_weights)
+        if self._init_then_wants_load(pretrained):
             _LOG.info('load model from: %s', self.pretrained)
             state_dict = torch.load(CHECKPOINT, map_location="cpu")
             state_dict['ln_post.weight'] = state_dict['norm.weight']
@@ -478,65 +430,33 @@ class ViT_ImageNet(nn.Module):
             _LOG.info('Missing keys: %s', msg.missing_keys)
             _LOG.info('Unexpected keys: %s', msg.unexpected_keys)
             self._last_load = msg
-        elif self.pretrained is None:
-            self.apply(_init_weights)
-        else:
-            raise TypeError('pretrained must be a str or None')
         for n, m in self.blocks.named_modules():
             if any(a in n for a in ("S_Adapter", "T_Adapter", "MLP_Adapter")) and n.endswith("D_fc2"):
                 nn.init.constant_(m.weight, 0)
                 nn.init.constant_(m.bias, 0)
-        self._frozen_cache = None
 
     @torch.jit.ignore
     def no_weight_decay(self):
         return {'pos_embed', 'temporal_embedding'}
 
-    def set_precision(self, precision: str):
-        """'bf16' (default) | 'fp32': the reference-precision verification mode (vit_imagenet_fp32.py: f32-MFMA kernels, the
-        same hand-written backward in fp32, plain autograd outputs)."""
-        if precision not in ('bf16', 'fp32'):
-            raise ValueError("precision must be 'bf16' or 'fp32'")
-        self.precision = precision
-        return self
-
-    def set_inference_precision(self, precision: str):
-        """'bf16' | 'fp8'; ViT_ImageNet has no fp8 path: 'fp8' warns once and runs bf16."""
-        if precision not in ('bf16', 'fp8'):
-            raise ValueError("inference precision must be 'bf16' or 'fp8'")
-        self.inference_precision = precision
-        return self
-
     # ---- operand staging ------------------------------------------------------------------------
-    def _param_names(self):
-        if getattr(self, "_names_cache", None) is None:
-            self._names_cache = [n for n, _ in self.named_parameters()]
-        return self._names_cache
-
     def _operand_params(self):
         """The parameters cached as bf16 operands across forwards (everything but the adapters, temporal_embedding, ln_post)."""
         return [p for n, p in self.named_parameters()
                 if "Adapter" not in n and n not in ("temporal_embedding", "ln_post.weight", "ln_post.bias")]
 
     def _frozen_operands(self):
-        """bf16 copies of the large weights; rebuilt when one of them changed: moved, changed version, or -- when any of them
-        trains -- an optimizer step that wrote them through raw pointers (``FlatAdamW.generation``, ``weights_epoch``)."""
-        from .dist import FlatAdamW
-        ps = self._operand_params()
-        key = tuple((p.data_ptr(), p._version) for p in ps)
-        if any(p.requires_grad for p in ps):     # (a FlatAdamW step writes through raw pointers: no version changes)
-            key += (self.weights_epoch, FlatAdamW.generation)
-        if self._frozen_cache is not None and self._frozen_cache[0] == key:
-            return self._frozen_cache[1]
+        """bf16 copies of the large weights, cached across forwards (``_cached_operands``)"""
+        return self._cached_operands(self._operand_params(), self._build_operands)
+
+    def _build_operands(self):
         D = self.embed_dim
         w, b = self.patch_embed.proj.weight, self.patch_embed.proj.bias
         f = lambda t: t.detach().float().contiguous()
-        out = dict(conv=_conv_operand(w), conv_b=f(b) if b is not None else torch.zeros(D, dtype=F32, device=w.device),
-                   cls=f(self.cls_token).view(D), pos=f(self.pos_embed).view(-1, D),
-                   blocks=[_Frozen(_frozen_view(blk)) for blk in self.blocks])
-        self._frozen_cache = (key, out)
-        self._cast_table = None
-        return out
+        self._cast_table = None          # (its entries point into the operands being replaced)
+        return dict(conv=_conv_operand(w), conv_b=f(b) if b is not None else torch.zeros(D, dtype=F32, device=w.device),
+                    cls=f(self.cls_token).view(D), pos=f(self.pos_embed).view(-1, D),
+                    blocks=[_Frozen(_frozen_view(blk)) for blk in self.blocks])
 
     def _stage_adapters(self, ops_, P):
         """Every adapter's weights -> its bf16 operand buffers (one ``aim_cast_multi`` launch); returns per-block _AdapterW."""
@@ -592,29 +512,6 @@ class ViT_ImageNet(nn.Module):
 
     # ---- forward --------------------------------------------------------------------------------
     def forward(self, x: torch.Tensor):
-        if not x.is_cuda:
-            raise RuntimeError("aim_amd.ViT_ImageNet runs on MI355X only (HIP kernels); there is no CPU fallback")
-        B, C, T, H, W = x.shape
-        if T != self.num_frames:
-            raise ValueError(f"expected {self.num_frames} frames, got {T}")
-        if C != 3 or H != self.img_size or W != self.img_size:
-            raise ValueError(f"expected input [B,3,{T},{self.img_size},{self.img_size}], got {tuple(x.shape)}")
-        if x.dtype not in (torch.float32, torch.float16, torch.bfloat16):
-            raise TypeError(f"ViT_ImageNet takes float clips, got {x.dtype}")
-        if x.dtype == torch.float16:
-            x = x.float()
-        x = x.contiguous()
-        if self.inference_precision == 'fp8' and not self._fp8_warned:
-            self._fp8_warned = True
-            _LOG.warning("fp8 inference was requested but ViT_ImageNet has no fp8 path: this forward runs bf16")
-        params = [p for _, p in self.named_parameters()]
-        if self.precision == 'fp32':
-            from .vit_imagenet_fp32 import _ViTImageNetFn32, forward_f32
-            if torch.is_grad_enabled() and any(p.requires_grad for p in params):
-                y = _ViTImageNetFn32.apply(self, x, *params)
-            else:
-                with torch.no_grad():
-                    y = forward_f32(self, x, dict(zip(self._param_names(), params)), ())[0]
-            return y.unsqueeze(-1).unsqueeze(-1)
-        y = _ViTImageNetFn.apply(self, torch.is_grad_enabled(), x, *params)      # [B, D, T]
-        return y.unsqueeze(-1).unsqueeze(-1)
+        x = self._check_clip(x, self.img_size)
+        from .vit_imagenet_fp32 import _ViTImageNetFn32, forward_f32
+        return self._dispatch(x, _ViTImageNetFn, _ViTImageNetFn32, forward_f32)

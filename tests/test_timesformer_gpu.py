@@ -194,17 +194,24 @@ def test_bf16_against_reference_fixture(tag):
 # real geometry against the restatement
 # ---------------------------------------------------------------------------------------------------------------------
 REAL = dict(input_resolution=224, patch_size=16, width=128, layers=2, heads=2)
+# ViT-L/14's patch at the tiny fixtures' size: K = 3 * 14 * 14 = 588 is no multiple of 64, so the bf16 conv operand is padded to
+# Kp = 640 and the conv weight gradient goes through its scratch buffer (patch 16 has K = 768 = Kp)
+PAD_K = dict(input_resolution=28, patch_size=14, width=128, layers=2, heads=2)
+GEOMS = dict(real=(REAL, 8, 1, 4400), padk=(PAD_K, 2, 2, 4502))       # name -> (geometry, frames, clips, seed)
 
 
 @functools.lru_cache(maxsize=None)
-def _real_case(masked):
-    """224 / 16 (N = 197), T = 8, one clip: the restatement in float64 on the CPU, with drawn factors or without."""
+def _real_case(geom, masked):
+    """224 / 16 (N = 197), T = 8, one clip, or 28 / 14 (N = 5), T = 2, two clips: the restatement in float64 on the CPU, with
+    drawn factors or without."""
     import aim_amd
-    T, N, seed = 8, 197, 4400
-    m = aim_amd.TimeSformer(num_frames=T, drop_path_rate=0.5, **REAL)
+    kw, T, B, seed = GEOMS[geom]
+    res = kw["input_resolution"]
+    N = (res // kw["patch_size"]) ** 2 + 1
+    m = aim_amd.TimeSformer(num_frames=T, drop_path_rate=0.5, **kw)
     shapes = [(n, tuple(p.shape)) for n, p in m.named_parameters()]
     sd = MG.synth_params(shapes, seed)
-    imgs, g = MG.randn((1, 3, T, 224, 224), seed + 1), MG.randn((1, REAL["width"], T, 1, 1), seed + 2)
+    imgs, g = MG.randn((B, 3, T, res, res), seed + 1), MG.randn((B, kw["width"], T, 1, 1), seed + 2)
     factors = None
     if masked:          # layer 1 of 2 has rate 0.5: factors 0 or 2, drawn here; every vector keeps and drops an entry
         gen = torch.Generator().manual_seed(seed + 3)
@@ -212,18 +219,22 @@ def _real_case(masked):
         factors = [(None, None, None), (draw(T), draw(N), draw(N))]
         assert all(0 < int((v == 0).sum()) < v.numel() for v in factors[1])
     P = {n: v.double().requires_grad_(True) for n, v in sd.items()}
-    y = REF.forward(P, imgs.double(), REAL["heads"], REAL["patch_size"], factors)
+    y = REF.forward(P, imgs.double(), kw["heads"], kw["patch_size"], factors)
     grads = torch.autograd.grad(y, [P[n] for n, _ in shapes], g.double())
     return sd, imgs, g, factors, y.detach(), dict(zip([n for n, _ in shapes], grads))
 
 
-@pytest.mark.parametrize("masked", [False, True], ids=["eval", "masks"])
-def test_real_geometry_against_restatement(masked):
+@pytest.mark.parametrize("geom, masked, precision", [
+    ("real", False, "bf16"), ("real", True, "bf16"), ("padk", False, "bf16"), ("padk", True, "bf16"),
+    ("padk", False, "fp32"), ("padk", True, "fp32")],
+    ids=["eval", "masks", "padk-eval", "padk-masks", "padk-fp32-eval", "padk-fp32-masks"])
+def test_real_geometry_against_restatement(geom, masked, precision):
     import aim_amd
-    sd, imgs, g, factors, y_ref, g_ref = _real_case(masked)
-    m = aim_amd.TimeSformer(num_frames=8, drop_path_rate=0.5, **REAL)
+    sd, imgs, g, factors, y_ref, g_ref = _real_case(geom, masked)
+    kw, T, _, _ = GEOMS[geom]
+    m = aim_amd.TimeSformer(num_frames=T, drop_path_rate=0.5, **kw)
     m.load_state_dict(sd, strict=True)
-    m = m.to(DEV).train(masked)
+    m = m.to(DEV).train(masked).set_precision(precision)
     if masked:
         _inject(m, factors)
     y = m(imgs.to(DEV))
@@ -231,8 +242,8 @@ def test_real_geometry_against_restatement(masked):
     errs = {"y": rel(y.detach(), y_ref)}
     errs.update({n: rel(gr, g_ref[n]) for (n, _), gr in zip(m.named_parameters(), grads)})
     worst = sorted(errs.items(), key=lambda kv: -kv[1])
-    print("real geometry", "masks" if masked else "eval", "worst:", [(k, f"{v:.2e}") for k, v in worst[:4]])
-    assert worst[0][1] <= BF16_BOUND, worst[:8]
+    print(geom, precision, "masks" if masked else "eval", "worst:", [(k, f"{v:.2e}") for k, v in worst[:4]])
+    assert worst[0][1] <= (BF16_BOUND if precision == "bf16" else F32_BOUND), worst[:8]
 
 
 # ---------------------------------------------------------------------------------------------------------------------

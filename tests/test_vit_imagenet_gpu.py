@@ -207,9 +207,10 @@ def test_fp32_against_reference_fixture(tag):
     _run(tag, 1e-5, precision="fp32")
 
 
-def test_fp32_no_grad_forward_matches_grad_forward():
+@pytest.mark.parametrize("precision", ["bf16", "fp32"])
+def test_fp32_no_grad_forward_matches_grad_forward(precision):
     m, T, train, seed = _build("a")
-    m.set_precision("fp32")
+    m.set_precision(precision)
     imgs = MG.randn((MG.B, 3, T, 32, 32), seed + 1).to(DEV)
     y1 = m(imgs).detach()
     with torch.no_grad():
