@@ -71,6 +71,10 @@ __device__ __forceinline__ bf16x4 pack4(float a, float b, float c, float d) {
     return r;
 }
 
+// the store that matches load4f: four consecutive row elements from an f32x4, as fp32 or rounded to bf16
+__device__ __forceinline__ void store4(float* p, f32x4 v) { *(f32x4*)p = v; }
+__device__ __forceinline__ void store4(bf16_t* p, f32x4 v) { *(bf16x4*)p = pack4(v[0], v[1], v[2], v[3]); }
+
 // four floats -> four OCP fp8 e4m3 bytes (saturating: |x| is clamped to the largest finite e4m3, 448; the inference
 // path's activations are cast this way by their producing kernel)
 __device__ __forceinline__ unsigned pack4_fp8(float a, float b, float c, float d) {

@@ -13,8 +13,10 @@
 //   (per-frame token sums for the broadcast S_Adapter term, bias gradients, bf16 weight staging).
 #include "aim_common.h"
 #include "aim_kernels_internal.h"
+#include "ln_row.h"
 
 namespace {
+using namespace ln_row;
 
 constexpr int MAXC = 8;
 
@@ -152,20 +154,6 @@ __global__ __launch_bounds__(256) void patchify_kernel(const TIN* __restrict__ i
     *(out_t*)(A + row * Kp + k0) = o;
 }
 
-__device__ __forceinline__ f32x4 embed_value(const bf16_t* tok, const float* cls, const float* pos, const float* tmp,
-                                             long long bt, int n, int t, int G2, int D, int c4) {
-    f32x4 v;
-    if (n == 0) {
-        v = *(const f32x4*)(cls + c4);
-    } else {
-        const bf16x4 tk = *(const bf16x4*)(tok + (bt * G2 + (n - 1)) * D + c4);
-        v = f32x4{(float)tk[0], (float)tk[1], (float)tk[2], (float)tk[3]};
-    }
-    v += *(const f32x4*)(pos + (long long)n * D + c4);
-    v += *(const f32x4*)(tmp + (long long)t * D + c4);
-    return v;
-}
-
 template <int NC>
 __global__ __launch_bounds__(256) void embed_ln_kernel(const bf16_t* __restrict__ tok, const float* __restrict__ cls,
                                                        const float* __restrict__ pos, const float* __restrict__ tmp,
@@ -178,44 +166,20 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const bf16_t* __restrict_
     const long long bt = row / N;
     const int n = (int)(row - bt * N), t = (int)(bt % T), nch = D >> 2;
     f32x4 v[NC];
-    float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        const int ch = lane + c * 64;
-        if (ch < nch) {
-            v[c] = embed_value(tok, cls, pos, tmp, bt, n, t, N - 1, D, ch * 4);
-            s += (v[c][0] + v[c][1]) + (v[c][2] + v[c][3]);
-        }
+    float s = 0.f, q = 0.f;
+    LN_ROW_CHUNKS(c, ch, NC, lane, nch) {
+        v[c] = embed_value(tok, cls, pos, tmp, bt, n, t, N - 1, D, ch * 4);
+        s += sum4(v[c]);
     }
-    const float mu = wave_sum(s) / (float)D;
-    float q = 0.f;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        const int ch = lane + c * 64;
-        if (ch < nch) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float d = v[c][e] - mu;
-                q += d * d;
-            }
-        }
-    }
-    const float rs = rsqrtf(wave_sum(q) / (float)D + eps);
+    const float mu = row_mean(s, D);
+    LN_ROW_CHUNKS(c, ch, NC, lane, nch) q = add_sqdev4(q, v[c], mu);
+    const float rs = row_rstd(q, D, eps);
     if (lane == 0) {
         mean[row] = mu;
         rstd[row] = rs;
     }
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        const int ch = lane + c * 64;
-        if (ch < nch) {
-            const f32x4 g = *(const f32x4*)(gamma + ch * 4), b = *(const f32x4*)(beta + ch * 4);
-            f32x4 y;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) y[e] = (v[c][e] - mu) * rs * g[e] + b[e];
-            *(f32x4*)(x + row * D + ch * 4) = y;
-        }
-    }
+    LN_ROW_CHUNKS(c, ch, NC, lane, nch)
+        store4(x + row * D + ch * 4, ln_affine4(v[c], mu, rs, *(const f32x4*)(gamma + ch * 4), *(const f32x4*)(beta + ch * 4)));
 }
 
 // grid (T, chunks): every wave walks rows (b, n) of frame-time t, accumulates ln_pre's input gradient
@@ -239,30 +203,24 @@ __global__ __launch_bounds__(256) void embed_bwd_kernel(const TDX* __restrict__ 
         const float mu = mean[row], rs = rstd[row];
         f32x4 g[NC], xh[NC];
         float s1 = 0.f, s2 = 0.f;
+        // Written out, not ln_bwd_chunk and ln_bwd_elem: here the compiler chooses what it contracts (it fuses part of the
+        // g xh products into s2, and the scale into the accumulation), and dtemporal keeps the bits of that choice.
+        LN_ROW_CHUNKS(c, ch, NC, lane, nch) {
+            const f32x4 v = embed_value(tok, cls, pos, tmp, bt, n, t, N - 1, D, ch * 4);
+            const f32x4 d = load4f(dx + row * D + ch * 4);
+            const f32x4 gm = *(const f32x4*)(gamma + ch * 4);
 #pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const int ch = lane + c * 64;
-            if (ch < nch) {
-                const f32x4 v = embed_value(tok, cls, pos, tmp, bt, n, t, N - 1, D, ch * 4);
-                const f32x4 d = load4f(dx + row * D + ch * 4);
-                const f32x4 gm = *(const f32x4*)(gamma + ch * 4);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    xh[c][e] = (v[e] - mu) * rs;
-                    g[c][e] = d[e] * gm[e];
-                    s1 += g[c][e];
-                    s2 += g[c][e] * xh[c][e];
-                }
+            for (int e = 0; e < 4; ++e) {
+                xh[c][e] = (v[e] - mu) * rs;
+                g[c][e] = d[e] * gm[e];
+                s1 += g[c][e];
+                s2 += g[c][e] * xh[c][e];
             }
         }
-        const float m1 = wave_sum(s1) / (float)D, m2 = wave_sum(s2) / (float)D;
+        const float m1 = row_mean(s1, D), m2 = row_mean(s2, D);
+        LN_ROW_CHUNKS(c, ch, NC, lane, nch) {
 #pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const int ch = lane + c * 64;
-            if (ch < nch) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc[c][e] += rs * (g[c][e] - m1 - xh[c][e] * m2);
-            }
+            for (int e = 0; e < 4; ++e) acc[c][e] += rs * (g[c][e] - m1 - xh[c][e] * m2);
         }
     }
     if (partial) {
@@ -270,33 +228,21 @@ __global__ __launch_bounds__(256) void embed_bwd_kernel(const TDX* __restrict__ 
         // to partial[t][blockIdx.y][D]; embed_bwd_finish_kernel adds the rows up in order (no atomics anywhere)
         __shared__ float red[3][NC * 256];
         if (wave > 0) {
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                const int ch = lane + c * 64;
-                if (ch < nch) *(f32x4*)(&red[wave - 1][ch * 4]) = acc[c];
-            }
+            LN_ROW_CHUNKS(c, ch, NC, lane, nch) *(f32x4*)(&red[wave - 1][ch * 4]) = acc[c];
         }
         __syncthreads();
         if (wave == 0) {
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                const int ch = lane + c * 64;
-                if (ch < nch) {
-                    f32x4 a = acc[c];
-                    for (int w = 0; w < 3; ++w) a += *(const f32x4*)(&red[w][ch * 4]);
-                    *(f32x4*)(partial + ((long long)t * gridDim.y + blockIdx.y) * D + ch * 4) = a;
-                }
+            LN_ROW_CHUNKS(c, ch, NC, lane, nch) {
+                f32x4 a = acc[c];
+                for (int w = 0; w < 3; ++w) a += *(const f32x4*)(&red[w][ch * 4]);
+                *(f32x4*)(partial + ((long long)t * gridDim.y + blockIdx.y) * D + ch * 4) = a;
             }
         }
         return;
     }
+    LN_ROW_CHUNKS(c, ch, NC, lane, nch) {
 #pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        const int ch = lane + c * 64;
-        if (ch < nch) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) atomicAdd(dtemporal + (long long)t * D + ch * 4 + e, acc[c][e]);
-        }
+        for (int e = 0; e < 4; ++e) atomicAdd(dtemporal + (long long)t * D + ch * 4 + e, acc[c][e]);
     }
 }
 
@@ -668,12 +614,10 @@ extern "C" int aim_embed_ln(const aim_bf16* tok, const float* cls, const float* 
     AIM_CHECK_ARG(B > 0 && T > 0 && N > 1 && D > 0 && (D % 4) == 0 && D <= MAXC * 256, "embed_ln: bad shape N=%d D=%d", N, D);
     AIM_CHECK_ARG(tok && cls && pos && temporal && gamma && beta && x && mean && rstd, "embed_ln: null pointer");
     const long long rows = (long long)B * T * N;
-#define AIM_EL(NC)                                                                                                 \
-    hipLaunchKernelGGL(embed_ln_kernel<NC>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream,      \
-                       (const bf16_t*)tok, cls, pos, temporal, gamma, beta, x, mean, rstd, B, T, N, D, eps)
-    const int nc = (D + 255) / 256;
-    if (nc <= 1) AIM_EL(1); else if (nc == 2) AIM_EL(2); else if (nc == 3) AIM_EL(3); else if (nc == 4) AIM_EL(4); else AIM_EL(8);
-#undef AIM_EL
+    nc_dispatch(D, [&](auto nc) {
+        hipLaunchKernelGGL(embed_ln_kernel<decltype(nc)::value>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+                           (const bf16_t*)tok, cls, pos, temporal, gamma, beta, x, mean, rstd, B, T, N, D, eps);
+    });
     AIM_CHECK_LAUNCH("aim_embed_ln");
     return 0;
 }
@@ -689,16 +633,15 @@ extern "C" int aim_embed_bwd(const void* dx, int dx_is_bf16, const aim_bf16* tok
     if (chunks > want) chunks = want;
     // with scratch ([T][chunks][D] fp32, aim_embed_bwd_workspace_bytes) the reduction is two-stage and bitwise reproducible
     float* partial = (workspace && workspace_bytes >= (int64_t)T * chunks * D * 4) ? workspace : nullptr;
-#define AIM_EB(NC)                                                                                                     \
-    if (dx_is_bf16)                                                                                                    \
-        hipLaunchKernelGGL((embed_bwd_kernel<NC, bf16_t>), dim3(T, chunks), dim3(256), 0, (hipStream_t)stream,          \
-                           (const bf16_t*)dx, (const bf16_t*)tok, cls, pos, temporal, gamma, mean, rstd, dtemporal, partial, B, T, N, D); \
-    else                                                                                                               \
-        hipLaunchKernelGGL((embed_bwd_kernel<NC, float>), dim3(T, chunks), dim3(256), 0, (hipStream_t)stream,           \
-                           (const float*)dx, (const bf16_t*)tok, cls, pos, temporal, gamma, mean, rstd, dtemporal, partial, B, T, N, D)
-    const int nc = (D + 255) / 256;
-    if (nc <= 1) AIM_EB(1); else if (nc == 2) AIM_EB(2); else if (nc == 3) AIM_EB(3); else if (nc == 4) AIM_EB(4); else AIM_EB(8);
-#undef AIM_EB
+    nc_dispatch(D, [&](auto nc) {
+        constexpr int NC = decltype(nc)::value;
+        if (dx_is_bf16)
+            hipLaunchKernelGGL((embed_bwd_kernel<NC, bf16_t>), dim3(T, chunks), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dx,
+                               (const bf16_t*)tok, cls, pos, temporal, gamma, mean, rstd, dtemporal, partial, B, T, N, D);
+        else
+            hipLaunchKernelGGL((embed_bwd_kernel<NC, float>), dim3(T, chunks), dim3(256), 0, (hipStream_t)stream, (const float*)dx,
+                               (const bf16_t*)tok, cls, pos, temporal, gamma, mean, rstd, dtemporal, partial, B, T, N, D);
+    });
     AIM_CHECK_LAUNCH("aim_embed_bwd");
     if (partial) {
         hipLaunchKernelGGL(embed_bwd_finish_kernel, dim3(T, (D + 63) / 64), dim3(256), 0, (hipStream_t)stream, partial, dtemporal,

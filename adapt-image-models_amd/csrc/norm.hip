@@ -7,8 +7,10 @@
 // fwd moves 4 B (x) + 2 B (bf16 y) per element.
 #include "aim_common.h"
 #include "aim_kernels_internal.h"
+#include "ln_row.h"
 
 namespace {
+using namespace ln_row;
 
 constexpr int MAXC = 8;  // float4 chunks per lane: D <= 8*4*64 = 2048 (template NC = chunks actually used)
 
@@ -25,60 +27,24 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const TX* __restrict__ x, l
     const int nch = D >> 2;
     const TX* xr = x + (long long)row * ldx;
     f32x4 v[NC];
-    float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        const int ch = lane + c * 64;
-        if (ch < nch) {
-            v[c] = load4f(xr + ch * 4);
-            s += (v[c][0] + v[c][1]) + (v[c][2] + v[c][3]);
-        }
+    float s = 0.f, q = 0.f;
+    LN_ROW_CHUNKS(c, ch, NC, lane, nch) {
+        v[c] = load4f(xr + ch * 4);
+        s += sum4(v[c]);
     }
-    const float mu = wave_sum(s) / (float)D;
-    float q = 0.f;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        const int ch = lane + c * 64;
-        if (ch < nch) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float d = v[c][e] - mu;
-                q += d * d;
-            }
-        }
-    }
-    const float rs = rsqrtf(wave_sum(q) / (float)D + eps);
+    const float mu = row_mean(s, D);
+    LN_ROW_CHUNKS(c, ch, NC, lane, nch) q = add_sqdev4(q, v[c], mu);
+    const float rs = row_rstd(q, D, eps);
     if (lane == 0) {
         if (mean) mean[row] = mu;
         if (rstd) rstd[row] = rs;
     }
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        const int ch = lane + c * 64;
-        if (ch < nch) {
-            const f32x4 g = *(const f32x4*)(gamma + ch * 4);
-            const f32x4 b = *(const f32x4*)(beta + ch * 4);
-            f32x4 y;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) y[e] = (v[c][e] - mu) * rs * g[e] + b[e];
-            if (yb) *(bf16x4*)(yb + (long long)row * ldy + ch * 4) = pack4(y[0], y[1], y[2], y[3]);
-            if (yf) *(f32x4*)(yf + (long long)row * ldy + ch * 4) = y;
-            if (y8) *(unsigned*)(y8 + (long long)row * ldy + ch * 4) = pack4_fp8(y[0], y[1], y[2], y[3]);
-        }
+    LN_ROW_CHUNKS(c, ch, NC, lane, nch) {
+        const f32x4 y = ln_affine4(v[c], mu, rs, *(const f32x4*)(gamma + ch * 4), *(const f32x4*)(beta + ch * 4));
+        if (yb) store4(yb + (long long)row * ldy + ch * 4, y);
+        if (yf) store4(yf + (long long)row * ldy + ch * 4, y);
+        if (y8) *(unsigned*)(y8 + (long long)row * ldy + ch * 4) = pack4_fp8(y[0], y[1], y[2], y[3]);
     }
-}
-
-// The last steps of one element of the LayerNorm backward in ONE fixed operation order, whatever the compiler would fuse in
-// the kernel around them: xhat * m2 folded into the subtraction (fma), the scale, then the residual as an addition of its own.
-// ln_bwd_kernel and ln_bwd_fsum_kernel both go through these, which is what makes their dx the same bits (left to the
-// compiler, one kernel fused rs * t + dres and all four xhat * m2, the other neither the first nor two of the four).
-__device__ __forceinline__ float ln_bwd_elem(float g, float xh, float m1, float m2, float rs) {
-#pragma clang fp contract(off)
-    return rs * __builtin_fmaf(-xh, m2, g - m1);
-}
-__device__ __forceinline__ f32x4 ln_add_res(f32x4 o, f32x4 r) {
-#pragma clang fp contract(off)
-    return o + r;
 }
 
 // dx = dres + rstd * (g - mean(g) - xhat * mean(g*xhat)),  g = dy * gamma
@@ -97,54 +63,35 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const TDY* __restrict__ dy,
     const float mu = mean[row], rs = rstd[row];
     f32x4 g[NC], xh[NC];
     float s1 = 0.f, s2 = 0.f;
+    // ln_bwd_chunk's arithmetic written out (ln_bwd_fsum_kernel calls it; dx_eq_layernorm_bwd holds the two to the same bits):
+    // through the helper the operands of s1's add come out in the other order and <1, float, .> needs 26 / 28 VGPRs for 24 / 26
+    LN_ROW_CHUNKS(c, ch, NC, lane, nch) {
+        const f32x4 d = load4f(dy + (long long)row * lddy + ch * 4);
+        const f32x4 xv = *(const f32x4*)(x + (long long)row * ldx + ch * 4);
+        const f32x4 gm = *(const f32x4*)(gamma + ch * 4);
 #pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        const int ch = lane + c * 64;
-        if (ch < nch) {
-            f32x4 d;
-            if constexpr (sizeof(TDY) == 4) {
-                d = *(const f32x4*)(dy + (long long)row * lddy + ch * 4);
-            } else {
-                const bf16x4 db = *(const bf16x4*)(dy + (long long)row * lddy + ch * 4);
-                d = f32x4{(float)db[0], (float)db[1], (float)db[2], (float)db[3]};
-            }
-            const f32x4 xv = *(const f32x4*)(x + (long long)row * ldx + ch * 4);
-            const f32x4 gm = *(const f32x4*)(gamma + ch * 4);
+        for (int e = 0; e < 4; ++e) {
+            xh[c][e] = (xv[e] - mu) * rs;
+            g[c][e] = d[e] * gm[e];
+            s1 += g[c][e];
+            s2 = __builtin_fmaf(g[c][e], xh[c][e], s2);
+        }
+        if (dgamma) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                xh[c][e] = (xv[e] - mu) * rs;
-                g[c][e] = d[e] * gm[e];
-                s1 += g[c][e];
-                s2 = __builtin_fmaf(g[c][e], xh[c][e], s2);
-            }
-            if (dgamma) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    atomicAdd(dgamma + ch * 4 + e, d[e] * xh[c][e]);
-                    atomicAdd(dbeta + ch * 4 + e, d[e]);
-                }
+                atomicAdd(dgamma + ch * 4 + e, d[e] * xh[c][e]);
+                atomicAdd(dbeta + ch * 4 + e, d[e]);
             }
         }
     }
-    const float m1 = wave_sum(s1) / (float)D, m2 = wave_sum(s2) / (float)D;
+    const float m1 = row_mean(s1, D), m2 = row_mean(s2, D);
+    LN_ROW_CHUNKS(c, ch, NC, lane, nch) {
+        f32x4 o;
 #pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        const int ch = lane + c * 64;
-        if (ch < nch) {
-            f32x4 o;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = ln_bwd_elem(g[c][e], xh[c][e], m1, m2, rs);
-            if (dres) {
-                if constexpr (sizeof(TDR) == 4) {
-                    o = ln_add_res(o, *(const f32x4*)(dres + (long long)row * lddres + ch * 4));
-                } else {
-                    const bf16x4 rb = *(const bf16x4*)(dres + (long long)row * lddres + ch * 4);
-                    o = ln_add_res(o, f32x4{(float)rb[0], (float)rb[1], (float)rb[2], (float)rb[3]});
-                }
-            }
-            if (dx) *(f32x4*)(dx + (long long)row * lddx + ch * 4) = o;
-            if (dxb) *(bf16x4*)(dxb + (long long)row * lddx + ch * 4) = pack4(o[0], o[1], o[2], o[3]);
-        }
+        for (int e = 0; e < 4; ++e) o[e] = ln_bwd_elem(g[c][e], xh[c][e], m1, m2, rs);
+        if (dres) o = ln_add_res(o, load4f(dres + (long long)row * lddres + ch * 4));
+        if (dx) store4(dx + (long long)row * lddx + ch * 4, o);
+        if (dxb) store4(dxb + (long long)row * lddx + ch * 4, o);
     }
 }
 
@@ -184,42 +131,23 @@ __global__ __launch_bounds__(256, (NC <= 4 ? 6 : 2)) void ln_bwd_fsum_kernel(con
         const float wt = w ? w[n] : 1.0f;
         f32x4 gv[NC], xh[NC];
         float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const int ch = lane + c * 64;
-            if (ch < nch) {
-                const bf16x4 db = *(const bf16x4*)(dy + row * lddy + ch * 4);
-                const f32x4 d = f32x4{(float)db[0], (float)db[1], (float)db[2], (float)db[3]};
-                const f32x4 xv = *(const f32x4*)(x + row * ldx + ch * 4);
-                const f32x4 gm = *(const f32x4*)(gamma + ch * 4);      // (L1-resident; held across rows it costs 12 VGPRs)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    xh[c][e] = (xv[e] - mu) * rs;
-                    gv[c][e] = d[e] * gm[e];
-                    s1 += gv[c][e];
-                    s2 = __builtin_fmaf(gv[c][e], xh[c][e], s2);
-                }
-            }
+        LN_ROW_CHUNKS(c, ch, NC, lane, nch) {      // (gamma: L1-resident; held across rows it costs 12 VGPRs)
+            const f32x4 d = load4f(dy + row * lddy + ch * 4);
+            ln_bwd_chunk(*(const f32x4*)(x + row * ldx + ch * 4), d, *(const f32x4*)(gamma + ch * 4), mu, rs, xh[c], gv[c], s1, s2);
         }
-        const float m1 = wave_sum(s1) / (float)D, m2 = wave_sum(s2) / (float)D;
+        const float m1 = row_mean(s1, D), m2 = row_mean(s2, D);
+        LN_ROW_CHUNKS(c, ch, NC, lane, nch) {
+            f32x4 o;
 #pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const int ch = lane + c * 64;
-            if (ch < nch) {
-                f32x4 o;
+            for (int e = 0; e < 4; ++e) o[e] = ln_bwd_elem(gv[c][e], xh[c][e], m1, m2, rs);
+            o = ln_add_res(o, load4f(dres + row * lddx + ch * 4));
+            const bf16x4 ob = pack4(o[0], o[1], o[2], o[3]);
+            *(bf16x4*)(dxb + row * lddx + ch * 4) = ob;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = ln_bwd_elem(gv[c][e], xh[c][e], m1, m2, rs);
-                const bf16x4 rb = *(const bf16x4*)(dres + row * lddx + ch * 4);
-                o = ln_add_res(o, f32x4{(float)rb[0], (float)rb[1], (float)rb[2], (float)rb[3]});
-                const bf16x4 ob = pack4(o[0], o[1], o[2], o[3]);
-                *(bf16x4*)(dxb + row * lddx + ch * 4) = ob;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) fs[c][e] += wt * (float)ob[e];      // the STORED (bf16) value, like a pass over dx
-            }
+            for (int e = 0; e < 4; ++e) fs[c][e] += wt * (float)ob[e];      // the STORED (bf16) value, like a pass over dx
         }
     }
-#pragma unroll
-    for (int c = 0; c < NC; ++c) red[wave][lane + c * 64] = fs[c];
+    LN_ROW_CHUNKS(c, ch, NC, lane, NC * 64) red[wave][ch] = fs[c];      // (every chunk: a dead one holds zeros)
     __syncthreads();
     for (int ch = threadIdx.x; ch < nch; ch += 256)
         *(f32x4*)(partial + (long long)bid * D + ch * 4) = (red[0][ch] + red[1][ch]) + (red[2][ch] + red[3][ch]);
@@ -227,21 +155,28 @@ __global__ __launch_bounds__(256, (NC <= 4 ? 6 : 2)) void ln_bwd_fsum_kernel(con
 
 }  // namespace
 
+// The one launch behind aim_layernorm_fwd, _fwd_fp8 and _fwd_x16, which have checked the shape and the pointers and differ in
+// the row type and in which of the outputs they leave null.  name: the entry point, for the launch error's message.
+template <typename TX>
+static int ln_fwd_launch(const char* name, const TX* x, int64_t ldx, const float* gamma, const float* beta, bf16_t* y_bf16,
+                         float* y_f32, uint8_t* y_fp8, int64_t ldy, float* mean, float* rstd, int rows, int D, float eps,
+                         void* stream) {
+    nc_dispatch(D, [&](auto nc) {
+        hipLaunchKernelGGL((ln_fwd_kernel<decltype(nc)::value, TX>), dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, x,
+                           (long long)ldx, gamma, beta, y_bf16, y_f32, (long long)ldy, mean, rstd, rows, D, eps, y_fp8);
+    });
+    AIM_CHECK_LAUNCH(name);
+    return 0;
+}
+
 extern "C" int aim_layernorm_fwd(const float* x, int64_t ldx, const float* gamma, const float* beta,
                                  aim_bf16* y_bf16, float* y_f32, int64_t ldy, float* mean, float* rstd,
                                  int rows, int D, float eps, void* stream) {
     AIM_CHECK_ARG(rows > 0 && D > 0 && (D % 4) == 0 && D <= MAXC * 256, "layernorm_fwd: bad shape rows=%d D=%d", rows, D);
     AIM_CHECK_ARG(x && gamma && beta && (y_bf16 || y_f32), "layernorm_fwd: null pointer");
     AIM_CHECK_ARG((ldx % 4) == 0 && (ldy % 4) == 0, "layernorm_fwd: strides must be multiples of 4");
-#define AIM_LN_FWD(NC)                                                                                            \
-    hipLaunchKernelGGL(ln_fwd_kernel<NC>, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, (long long)ldx, \
-                       gamma, beta, (bf16_t*)y_bf16, y_f32, (long long)ldy, mean, rstd, rows, D, eps)
-    const int nc = (D + 255) / 256;
-    if (nc <= 1) AIM_LN_FWD(1); else if (nc == 2) AIM_LN_FWD(2); else if (nc == 3) AIM_LN_FWD(3);
-    else if (nc == 4) AIM_LN_FWD(4); else AIM_LN_FWD(8);
-#undef AIM_LN_FWD
-    AIM_CHECK_LAUNCH("aim_layernorm_fwd");
-    return 0;
+    return ln_fwd_launch("aim_layernorm_fwd", x, ldx, gamma, beta, (bf16_t*)y_bf16, y_f32, nullptr, ldy, mean, rstd, rows, D, eps,
+                         stream);
 }
 
 extern "C" int aim_layernorm_fwd_fp8(const float* x, int64_t ldx, const float* gamma, const float* beta, uint8_t* y_fp8,
@@ -249,15 +184,8 @@ extern "C" int aim_layernorm_fwd_fp8(const float* x, int64_t ldx, const float* g
     AIM_CHECK_ARG(rows > 0 && D > 0 && (D % 4) == 0 && D <= MAXC * 256, "layernorm_fwd_fp8: bad shape rows=%d D=%d", rows, D);
     AIM_CHECK_ARG(x && gamma && beta && y_fp8, "layernorm_fwd_fp8: null pointer");
     AIM_CHECK_ARG((ldx % 4) == 0 && (ldy % 4) == 0, "layernorm_fwd_fp8: strides must be multiples of 4");
-#define AIM_LN_FWD8(NC)                                                                                           \
-    hipLaunchKernelGGL(ln_fwd_kernel<NC>, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, (long long)ldx, \
-                       gamma, beta, (bf16_t*)nullptr, (float*)nullptr, (long long)ldy, (float*)nullptr, (float*)nullptr, rows, D, eps, y_fp8)
-    const int nc = (D + 255) / 256;
-    if (nc <= 1) AIM_LN_FWD8(1); else if (nc == 2) AIM_LN_FWD8(2); else if (nc == 3) AIM_LN_FWD8(3);
-    else if (nc == 4) AIM_LN_FWD8(4); else AIM_LN_FWD8(8);
-#undef AIM_LN_FWD8
-    AIM_CHECK_LAUNCH("aim_layernorm_fwd_fp8");
-    return 0;
+    return ln_fwd_launch("aim_layernorm_fwd_fp8", x, ldx, gamma, beta, nullptr, nullptr, y_fp8, ldy, nullptr, nullptr, rows, D,
+                         eps, stream);
 }
 
 // bf16 rows in (the fp8 inference path's residual stream); y as bf16 and / or f32 and / or fp8
@@ -266,16 +194,8 @@ extern "C" int aim_layernorm_fwd_x16(const aim_bf16* x, int64_t ldx, const float
     AIM_CHECK_ARG(rows > 0 && D > 0 && (D % 4) == 0 && D <= MAXC * 256, "layernorm_fwd_x16: bad shape rows=%d D=%d", rows, D);
     AIM_CHECK_ARG(x && gamma && beta && (y_bf16 || y_f32 || y_fp8), "layernorm_fwd_x16: null pointer");
     AIM_CHECK_ARG((ldx % 4) == 0 && (ldy % 4) == 0, "layernorm_fwd_x16: strides must be multiples of 4");
-#define AIM_LN_FWDX(NC)                                                                                              \
-    hipLaunchKernelGGL((ln_fwd_kernel<NC, bf16_t>), dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, \
-                       (long long)ldx, gamma, beta, (bf16_t*)y_bf16, y_f32, (long long)ldy, (float*)nullptr, (float*)nullptr, \
-                       rows, D, eps, y_fp8)
-    const int nc = (D + 255) / 256;
-    if (nc <= 1) AIM_LN_FWDX(1); else if (nc == 2) AIM_LN_FWDX(2); else if (nc == 3) AIM_LN_FWDX(3);
-    else if (nc == 4) AIM_LN_FWDX(4); else AIM_LN_FWDX(8);
-#undef AIM_LN_FWDX
-    AIM_CHECK_LAUNCH("aim_layernorm_fwd_x16");
-    return 0;
+    return ln_fwd_launch("aim_layernorm_fwd_x16", (const bf16_t*)x, ldx, gamma, beta, (bf16_t*)y_bf16, y_f32, y_fp8, ldy, nullptr,
+                         nullptr, rows, D, eps, stream);
 }
 
 namespace {
@@ -348,20 +268,18 @@ extern "C" int aim_layernorm_bwd(const void* dy, int dy_is_bf16, int64_t lddy, c
         dgamma = nullptr;
         dbeta = nullptr;
     }
-#define AIM_LN_BWD_T(NC, TDY, TDR)                                                                                  \
+    nc_dispatch(D, [&](auto nc) {
+        constexpr int NC = decltype(nc)::value;
+#define AIM_LN_BWD_T(TDY, TDR)                                                                                      \
     hipLaunchKernelGGL((ln_bwd_kernel<NC, TDY, TDR>), dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream,        \
                        (const TDY*)dy, (long long)lddy, x, (long long)ldx, gamma, mean, rstd, (const TDR*)dres,       \
                        (long long)lddres, dx, (bf16_t*)dx_bf16, (long long)lddx, dgamma, dbeta, rows, D)
-#define AIM_LN_BWD(NC)                                                                                              \
-    if (dy_is_bf16 && dres_is_bf16) AIM_LN_BWD_T(NC, bf16_t, bf16_t);                                               \
-    else if (dy_is_bf16) AIM_LN_BWD_T(NC, bf16_t, float);                                                           \
-    else if (dres_is_bf16) AIM_LN_BWD_T(NC, float, bf16_t);                                                         \
-    else AIM_LN_BWD_T(NC, float, float)
-    const int nc = (D + 255) / 256;
-    if (nc <= 1) AIM_LN_BWD(1); else if (nc == 2) AIM_LN_BWD(2); else if (nc == 3) AIM_LN_BWD(3);
-    else if (nc == 4) AIM_LN_BWD(4); else AIM_LN_BWD(8);
-#undef AIM_LN_BWD
+        if (dy_is_bf16 && dres_is_bf16) AIM_LN_BWD_T(bf16_t, bf16_t);
+        else if (dy_is_bf16) AIM_LN_BWD_T(bf16_t, float);
+        else if (dres_is_bf16) AIM_LN_BWD_T(float, bf16_t);
+        else AIM_LN_BWD_T(float, float);
 #undef AIM_LN_BWD_T
+    });
     AIM_CHECK_LAUNCH("aim_layernorm_bwd");
     return 0;
 }
@@ -374,14 +292,11 @@ extern "C" int aim_layernorm_bwd_fsum(const aim_bf16* dy, int64_t lddy, const fl
                   "layernorm_bwd_fsum: bad shape frames=%d ntok=%d groups=%d D=%d", frames, ntok, groups, D);
     AIM_CHECK_ARG(dy && x && gamma && mean && rstd && dres && dx_bf16 && fsum_partial, "layernorm_bwd_fsum: null pointer");
     AIM_CHECK_ARG((ldx % 4) == 0 && (lddy % 4) == 0 && (lddx % 4) == 0, "layernorm_bwd_fsum: strides must be multiples of 4");
-#define AIM_LN_FS(NC)                                                                                                  \
-    hipLaunchKernelGGL(ln_bwd_fsum_kernel<NC>, dim3(frames * groups), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy, \
-                       (long long)lddy, x, (long long)ldx, gamma, mean, rstd, (const bf16_t*)dres, (bf16_t*)dx_bf16,    \
-                       (long long)lddx, w, fsum_partial, ntok, groups, D)
-    const int nc = (D + 255) / 256;
-    if (nc <= 1) AIM_LN_FS(1); else if (nc == 2) AIM_LN_FS(2); else if (nc == 3) AIM_LN_FS(3);
-    else if (nc == 4) AIM_LN_FS(4); else AIM_LN_FS(8);
-#undef AIM_LN_FS
+    nc_dispatch(D, [&](auto nc) {
+        hipLaunchKernelGGL(ln_bwd_fsum_kernel<decltype(nc)::value>, dim3(frames * groups), dim3(256), 0, (hipStream_t)stream,
+                           (const bf16_t*)dy, (long long)lddy, x, (long long)ldx, gamma, mean, rstd, (const bf16_t*)dres,
+                           (bf16_t*)dx_bf16, (long long)lddx, w, fsum_partial, ntok, groups, D);
+    });
     AIM_CHECK_LAUNCH("aim_layernorm_bwd_fsum");
     return 0;
 }

@@ -10,6 +10,7 @@
 //   partial slabs, then an ordered sum over the slabs).
 #include "aim_common.h"
 #include "aim_kernels_internal.h"
+#include "ln_row.h"
 
 namespace {
 
@@ -228,6 +229,7 @@ extern "C" int aim_layernorm_gb_bwd(const void* dy, int dy_is_bf16, int64_t lddy
 }
 
 namespace {
+using namespace ln_row;
 
 // ---- TimeSformer (reference timesformer.py:196-208): the full backward of the fused stem x = ln_pre([cls ; tok] + pos + temporal)
 // (aim_embed_ln / aim_embed_ln_f32), for a model whose stem trains ----
@@ -258,43 +260,29 @@ __global__ __launch_bounds__(256) void embed_ln_bwd_rows_kernel(const TX* __rest
         const float mu = mean[row], rs = rstd[row];
         f32x4 g[NC], xh[NC];
         float s1 = 0.f, s2 = 0.f;
+        // Written out, as in embed_bwd_kernel, not ln_bwd_chunk and ln_bwd_elem: what the compiler contracts here (part of the
+        // g xh products into s2) is what the bits of dtok and of the three sums are.
+        LN_ROW_CHUNKS(c, ch, NC, lane, nch) {
+            const f32x4 v = embed_value(tok, cls, pos, tmp, bt, n, t, N - 1, D, ch * 4);
+            const f32x4 d = load4f(dx + row * D + ch * 4);
+            const f32x4 gm = *(const f32x4*)(gamma + ch * 4);
 #pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const int ch = lane + c * 64;
-            if (ch < nch) {
-                f32x4 v = n == 0 ? *(const f32x4*)(cls + ch * 4) : load4f(tok + (bt * (N - 1) + (n - 1)) * D + ch * 4);
-                v += *(const f32x4*)(pos + (long long)n * D + ch * 4);
-                v += *(const f32x4*)(tmp + (long long)t * D + ch * 4);
-                const f32x4 d = load4f(dx + row * D + ch * 4);
-                const f32x4 gm = *(const f32x4*)(gamma + ch * 4);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    xh[c][e] = (v[e] - mu) * rs;
-                    g[c][e] = d[e] * gm[e];
-                    s1 += g[c][e];
-                    s2 += g[c][e] * xh[c][e];
-                    adg[c][e] = fmaf(d[e], xh[c][e], adg[c][e]);
-                    adb[c][e] += d[e];
-                }
+            for (int e = 0; e < 4; ++e) {
+                xh[c][e] = (v[e] - mu) * rs;
+                g[c][e] = d[e] * gm[e];
+                s1 += g[c][e];
+                s2 += g[c][e] * xh[c][e];
+                adg[c][e] = fmaf(d[e], xh[c][e], adg[c][e]);
+                adb[c][e] += d[e];
             }
         }
-        const float m1 = wave_sum(s1) / (float)D, m2 = wave_sum(s2) / (float)D;
+        const float m1 = row_mean(s1, D), m2 = row_mean(s2, D);
+        LN_ROW_CHUNKS(c, ch, NC, lane, nch) {
+            f32x4 du;
 #pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const int ch = lane + c * 64;
-            if (ch < nch) {
-                f32x4 du;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) du[e] = rs * (g[c][e] - m1 - xh[c][e] * m2);
-                adu[c] += du;
-                if (dtok && n > 0) {
-                    TX* dst = dtok + (bt * (N - 1) + (n - 1)) * D + ch * 4;
-                    if constexpr (sizeof(TX) == 4)
-                        *(f32x4*)dst = du;
-                    else
-                        *(bf16x4*)dst = pack4(du[0], du[1], du[2], du[3]);
-                }
-            }
+            for (int e = 0; e < 4; ++e) du[e] = rs * (g[c][e] - m1 - xh[c][e] * m2);
+            adu[c] += du;
+            if (dtok && n > 0) store4(dtok + (bt * (N - 1) + (n - 1)) * D + ch * 4, du);
         }
     }
     // the four waves' sums meet in LDS and are added in wave order; one quantity at a time (NC = 8: 24 KB of LDS)
@@ -304,22 +292,14 @@ __global__ __launch_bounds__(256) void embed_ln_bwd_rows_kernel(const TX* __rest
         f32x4* acc = q == 0 ? adu : (q == 1 ? adg : adb);
         if (q > 0) __syncthreads();
         if (wave > 0) {
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                const int ch = lane + c * 64;
-                if (ch < nch) *(f32x4*)(&red[wave - 1][ch * 4]) = acc[c];
-            }
+            LN_ROW_CHUNKS(c, ch, NC, lane, nch) *(f32x4*)(&red[wave - 1][ch * 4]) = acc[c];
         }
         __syncthreads();
         if (wave == 0) {
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                const int ch = lane + c * 64;
-                if (ch < nch) {
-                    f32x4 a = acc[c];
-                    for (int w = 0; w < 3; ++w) a += *(const f32x4*)(&red[w][ch * 4]);
-                    *(f32x4*)(part + (q * NT + p) * D + ch * 4) = a;
-                }
+            LN_ROW_CHUNKS(c, ch, NC, lane, nch) {
+                f32x4 a = acc[c];
+                for (int w = 0; w < 3; ++w) a += *(const f32x4*)(&red[w][ch * 4]);
+                *(f32x4*)(part + (q * NT + p) * D + ch * 4) = a;
             }
         }
     }
@@ -387,16 +367,15 @@ extern "C" int aim_embed_ln_bwd(const void* dx, int is_bf16, const void* tok, co
                   "embed_ln_bwd: workspace of %lld bytes needed", (long long)aim_embed_ln_bwd_workspace_bytes(B, T, N, D));
     hipStream_t st = (hipStream_t)stream;
     const int P = N * T;
-#define AIM_ELB(NC)                                                                                                       \
-    if (is_bf16)                                                                                                          \
-        hipLaunchKernelGGL((embed_ln_bwd_rows_kernel<NC, bf16_t>), dim3(N, T), dim3(256), 0, st, (const bf16_t*)dx,         \
-                           (const bf16_t*)tok, cls, pos, temporal, gamma, mean, rstd, (bf16_t*)dtok, workspace, B, T, N, D); \
-    else                                                                                                                  \
-        hipLaunchKernelGGL((embed_ln_bwd_rows_kernel<NC, float>), dim3(N, T), dim3(256), 0, st, (const float*)dx,           \
-                           (const float*)tok, cls, pos, temporal, gamma, mean, rstd, (float*)dtok, workspace, B, T, N, D)
-    const int nc = (D + 255) / 256;
-    if (nc <= 1) AIM_ELB(1); else if (nc == 2) AIM_ELB(2); else if (nc == 3) AIM_ELB(3); else if (nc == 4) AIM_ELB(4); else AIM_ELB(8);
-#undef AIM_ELB
+    ln_row::nc_dispatch(D, [&](auto nc) {
+        constexpr int NC = decltype(nc)::value;
+        if (is_bf16)
+            hipLaunchKernelGGL((embed_ln_bwd_rows_kernel<NC, bf16_t>), dim3(N, T), dim3(256), 0, st, (const bf16_t*)dx,
+                               (const bf16_t*)tok, cls, pos, temporal, gamma, mean, rstd, (bf16_t*)dtok, workspace, B, T, N, D);
+        else
+            hipLaunchKernelGGL((embed_ln_bwd_rows_kernel<NC, float>), dim3(N, T), dim3(256), 0, st, (const float*)dx,
+                               (const float*)tok, cls, pos, temporal, gamma, mean, rstd, (float*)dtok, workspace, B, T, N, D);
+    });
     AIM_CHECK_LAUNCH("aim_embed_ln_bwd(rows)");
     if (dcls || dpos || dtemporal) {
         hipLaunchKernelGGL(embed_ln_bwd_finish_kernel, dim3((D + 63) / 64, N + T), dim3(256), 0, st, workspace, dcls, dpos,

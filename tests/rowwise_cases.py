@@ -84,20 +84,20 @@ def _cdiv(a, b):
 
 
 def ln_nc(D: int) -> int:
-    """csrc/norm.hip:236-238 (and :252, :270, :357, :378; embed_misc.hip:672, :697): float4 chunks per lane."""
+    """csrc/ln_row.h::nc_dispatch, the one ladder behind every launch of the wave-per-row kernels: float4 chunks per lane."""
     nc = (D + 255) // 256
     return nc if nc <= 4 else 8
 
 
 def ln_dparam_route(rows: int, has_dgamma: bool):
-    """csrc/norm.hip:337 (AIM_LN_DPARAM_ROWS = 8192, :325): who adds dgamma / dbeta."""
+    """csrc/norm.hip::aim_layernorm_bwd (AIM_LN_DPARAM_ROWS = 8192): who adds dgamma / dbeta."""
     if not has_dgamma:
         return None
     return "ordered" if rows <= 8192 else "atomic"
 
 
 def colsum_route(M: int, C: int, ldx: int, workspace_bytes: int):
-    """csrc/embed_misc.hip:732-757: (route, row blocks, rows per block)."""
+    """csrc/embed_misc.hip::aim_colsum_bf16: (route, row blocks, rows per block)."""
     if C % 8 == 0 and C <= 2048 and ldx % 8 == 0:
         rpb = max(64, (M + 1023) // 1024)
         P = _cdiv(M, rpb)
@@ -111,25 +111,25 @@ def colsum_route(M: int, C: int, ldx: int, workspace_bytes: int):
 
 
 def embed_bwd_chunks(B: int, T: int, N: int) -> int:
-    """csrc/embed_misc.hip:685-687: row chunks (grid y) of embed_bwd_kernel."""
+    """csrc/embed_misc.hip::aim_embed_bwd (and aim_embed_bwd_workspace_bytes): row chunks (grid y) of embed_bwd_kernel."""
     return min((B * N + 3) // 4, (2048 + T - 1) // T)
 
 
 def gb_slabs(rows: int):
-    """csrc/vit_imagenet.hip:101-104, :225-226: (rows per slab, slabs)."""
+    """csrc/vit_imagenet.hip::gb_rows_per_slab and aim_layernorm_gb_bwd: (rows per slab, slabs)."""
     rps = max(16, (rows + 1023) // 1024)
     return rps, _cdiv(rows, rps)
 
 
 def cast_route(transpose: bool, ldd: int, C: int) -> str:
-    """csrc/embed_misc.hip:765-774."""
+    """csrc/embed_misc.hip::aim_cast_bf16."""
     if transpose:
         return "transpose"
     return "strided" if ldd and ldd != C else "dense"
 
 
 def cast_multi_route(desc) -> str:
-    """csrc/embed_misc.hip:555-596; desc = (transpose, R, C, ldd, src 16-byte aligned, dst 8-byte aligned)."""
+    """csrc/embed_misc.hip::cast_multi_kernel; desc = (transpose, R, C, ldd, src 16-byte aligned, dst 8-byte aligned)."""
     tr, R, C, ldd, s16, d8 = desc
     if tr == 0 and C % 4 == 0 and ldd % 4 == 0 and s16 and d8:
         return "wide4"
@@ -262,7 +262,7 @@ def emu_ln_bwd(dy, x, G, mu, rs, dres, NC, mut=None):
         m1 = torch.zeros_like(m1)
     if mut == "no_m2":
         m2 = torch.zeros_like(m2)
-    # csrc/norm.hip::ln_bwd_elem: fma(-xh, m2, g - m1) (an exact product in float64, rounded once), the scale, then the residual
+    # csrc/ln_row.h::ln_bwd_elem: fma(-xh, m2, g - m1) (an exact product in float64, rounded once), the scale, then the residual
     t = ((g - m1[:, None]).double() - xh.double() * m2[:, None].double()).float()
     if dres is not None and mut == "dres_before_scale":
         return rs[:, None] * (t + dres), xh
