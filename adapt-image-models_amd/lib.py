@@ -141,9 +141,15 @@ SIGNATURES = {
     "aim_layernorm_gb_bwd": [P, I, L, P, L, P, P, P, P, I, I, P, L, P],
     "aim_embed_ln_bwd_workspace_bytes": [I, I, I, I],
     "aim_embed_ln_bwd": [P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P, L, P],
+    "aim_swin_win_attn_fwd": [P, P, P, P, I, I, I, I, I, P],
+    "aim_swin_win_attn_bwd": [P, P, P, P, P, P, I, I, I, I, I, P, L, P],
+    "aim_swin_tattn_fwd": [P, P, P, P, I, I, I, I, P],
+    "aim_swin_tattn_bwd": [P, P, P, P, P, P, I, I, I, I, P, L, P],
+    "aim_swin_attn_bwd_workspace_bytes": [I, I, I],
+    "aim_swin_bias_scatter": [P, P, P, I, I, I, P],
 }
 
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 
 def load_library():

@@ -493,6 +493,77 @@ def win_attn_bwd_cut(qkv, out, dout, lse, delta, dqkv, B, T, N, H, window, shift
     _win_attn_bwd("aim_win_attn_bwd_cut", qkv, out, dout, lse, delta, dqkv, B, T, N, H, window, shift, P)
 
 
+def swin_attn_cap(S: int) -> int:
+    """token slots per sequence of the Swin attention kernels' lse rows (include/aim_kernels.h, ABI 18)"""
+    return 32 if S <= 32 else 64
+
+
+def _swin_bwd(entry, geom, rows, nseq, H, S, qkv, bias, dout, lse, dqkv, dbias):
+    _chk(qkv, BF16, "qkv"); _chk(dout, BF16, "dout"); _chk(dqkv, BF16, "dqkv"); _chk(dbias, F32, "dbias")
+    _swin_sizes(entry, qkv, bias, dout, lse, rows, nseq, H, S)
+    if not dqkv.is_contiguous() or dqkv.numel() != qkv.numel() or \
+            (dbias is not None and (not dbias.is_contiguous() or dbias.numel() != bias.numel())):
+        raise ValueError(f"{entry}: dqkv / dbias must be contiguous with the sizes of qkv / bias")
+    lib = load_library()
+    nbytes = lib.aim_swin_attn_bwd_workspace_bytes(nseq, H, S) if dbias is not None else 0
+    ws = torch.empty((nbytes // 4,), dtype=F32, device=qkv.device) if nbytes else None
+    check(getattr(lib, entry)(qkv.data_ptr(), bias.data_ptr(), dout.data_ptr(), lse.data_ptr(), dqkv.data_ptr(), _p(dbias), *geom,
+                              _p(ws), nbytes, _stream()), entry)
+
+
+def _swin_sizes(entry, qkv, bias, out, lse, rows, nseq, H, S):
+    """the sizes of the buffers every Swin attention entry shares (``out``: out of the forward, dout of the backward)"""
+    _chk(qkv, BF16, "qkv"); _chk(bias, F32, "bias"); _chk(out, BF16, "out"); _chk(lse, F32, "lse")
+    C = 32 * H
+    want = dict(qkv=(qkv, rows * 3 * C), bias=(bias, H * S * S), out=(out, rows * C), lse=(lse, nseq * H * swin_attn_cap(S)))
+    for n_, (t_, numel) in want.items():
+        if not t_.is_contiguous() or t_.numel() != numel:
+            raise ValueError(f"{entry}: {n_} must be contiguous with {numel} elements, got {tuple(t_.shape)}")
+
+
+def swin_win_attn_fwd(qkv, bias, out, lse, frames, res, H, window, shift):
+    """Swin window attention (head width 32) on the fused qkv [frames*res*res, 96 H]: the windows of the grid rolled by
+    -shift, masked pairs at weight exactly 0, ``bias`` [H, S, S] f32 (S = window^2).  out [rows, 32 H] bf16; lse
+    [frames*(res/window)^2, H, swin_attn_cap(S)] f32 (base 2)."""
+    if window > 0 and res > 0 and res % window == 0:
+        _swin_sizes("swin_win_attn_fwd", qkv, bias, out, lse, frames * res * res, frames * (res // window) ** 2, H, window * window)
+    check(load_library().aim_swin_win_attn_fwd(qkv.data_ptr(), bias.data_ptr(), out.data_ptr(), lse.data_ptr(), frames, res, H,
+                                               window, shift, _stream()), "aim_swin_win_attn_fwd")
+
+
+def swin_win_attn_bwd(qkv, bias, dout, lse, dqkv, dbias, frames, res, H, window, shift):
+    """backward of swin_win_attn_fwd from d(out) and the forward's lse: writes dqkv [rows, 96 H] and, unless None, the dense
+    bias gradient dbias [H, S, S] (two-stage fixed-order sum over the windows: equal bits on every run)."""
+    _swin_bwd("aim_swin_win_attn_bwd", (frames, res, H, window, shift), frames * res * res, frames * (res // window) ** 2, H,
+              window * window, qkv, bias, dout, lse, dqkv, dbias)
+
+
+def swin_tattn_fwd(qkv, bias, out, lse, B, T, L, H):
+    """Swin temporal attention (head width 32) over the T <= 32 frame tokens of every (clip, position) of the fused qkv
+    [B*T*L, 96 H]; ``bias`` [H, T, T] f32.  out [rows, 32 H] bf16; lse [B*L, H, 32] f32 (base 2)."""
+    if 0 < T <= 32:
+        _swin_sizes("swin_tattn_fwd", qkv, bias, out, lse, B * T * L, B * L, H, T)
+    check(load_library().aim_swin_tattn_fwd(qkv.data_ptr(), bias.data_ptr(), out.data_ptr(), lse.data_ptr(), B, T, L, H, _stream()),
+          "aim_swin_tattn_fwd")
+
+
+def swin_tattn_bwd(qkv, bias, dout, lse, dqkv, dbias, B, T, L, H):
+    """backward of swin_tattn_fwd: writes dqkv and, unless None, the dense bias gradient dbias [H, T, T]."""
+    _swin_bwd("aim_swin_tattn_bwd", (B, T, L, H), B * T * L, B * L, H, T, qkv, bias, dout, lse, dqkv, dbias)
+
+
+def swin_bias_scatter(dense, index, dtable):
+    """dtable [ntable, H] f32 += the dense bias gradient ``dense`` [H, S, S] folded along ``index`` [S*S] int32 (the
+    relative-position index), entries of one table row summed in ascending order."""
+    _chk(dense, F32, "dense"); _chk(index, torch.int32, "index"); _chk(dtable, F32, "dtable")
+    H, SS = dense.shape[0], dense.shape[1] * dense.shape[2]
+    if not (dense.is_contiguous() and index.is_contiguous() and dtable.is_contiguous()) or index.numel() != SS \
+            or dtable.dim() != 2 or dtable.shape[1] != H:
+        raise ValueError("swin_bias_scatter: dense [H, S, S], index [S*S] and dtable [ntable, H], all contiguous")
+    check(load_library().aim_swin_bias_scatter(dense.data_ptr(), index.data_ptr(), dtable.data_ptr(), H, SS, dtable.shape[0],
+                                               _stream()), "aim_swin_bias_scatter")
+
+
 def attn_fwd_cls(qkv, out_cls, lse_cls, BT, N, H):
     """attn_fwd for the class query of every (frame, head) alone: out_cls [BT, D], lse_cls [BT, H]."""
     _chk(qkv, BF16, "qkv"); _chk(out_cls, BF16, "out_cls"); _chk(lse_cls, F32, "lse_cls")

@@ -147,6 +147,8 @@ def register_into_mmaction() -> bool:
     MB.register_module(name="ViT_CLIP_ZEROI2V", force=True, module=ViT_CLIP_ZEROI2V)       # vit_clip_zeroI2V.py:361
     from .timesformer import TimeSformer
     MB.register_module(name="TimeSformer", force=True, module=TimeSformer)                 # timesformer.py:86
+    from .swin2d_adapter import SwinTransformer2D_Adapter
+    MB.register_module(name="SwinTransformer2D_Adapter", force=True, module=SwinTransformer2D_Adapter)      # swin2d_adapter.py:600
     return True
 
 

@@ -32,7 +32,7 @@ extern "C" {
 
 typedef uint16_t aim_bf16;
 
-#define AIM_ABI_VERSION 17
+#define AIM_ABI_VERSION 18
 
 int aim_version(void);                /* == AIM_ABI_VERSION */
 const char* aim_last_error(void);     /* message of the last failing call on this thread */
@@ -627,6 +627,33 @@ int aim_embed_ln_bwd(const void* dx, int is_bf16, const void* tok, const float* 
                      const float* gamma, const float* mean, const float* rstd, void* dtok, float* dcls, float* dpos,
                      float* dtemporal, float* dgamma, float* dbeta, int B, int T, int N, int D, float* workspace,
                      int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * SwinTransformer2D_Adapter (reference swin2d_adapter.py; ABI 18): attention at head width 32 over sequences of at most 64
+ * tokens under a dense additive bias, on the fused qkv [rows, 3 C] bf16 (C = 32 H, frame-major rows (frame, h, w)).
+ *   win   : the window x window tokens of each window of the res x res grid rolled by -shift (:372-395); roll, partition and
+ *           their inverses are addresses.  A (query, key) pair that the reference's attn_mask gives -100 has the weight
+ *           exactly 0.  bias [H, S, S] f32, S = window^2, in window-local token order.  frames = B T'.
+ *   tattn : the T frame tokens of each (clip, position) (:361-366): token t of (b, n) is row (b T + t) L + n; bias [H, T, T].
+ * fwd writes out [rows, C] bf16 and lse [sequences, H, CAP] f32 (base 2; CAP = 32 where S <= 32, else 64).  bwd (from qkv, dout [rows, C] and the forward's lse; delta = sum_j p_j dP_j) writes dqkv
+ * [rows, 3 C] bf16 (all three parts of every row) and, where dbias is not NULL, the dense bias gradient dbias [H, S, S] =
+ * sum over sequences of P o (dP - delta): per-chunk partial sums in the workspace, added in a fixed order (no atomics; equal
+ * bits on every run).  The 32^-1/2 scale is applied to the fp32 score; p and dS are rounded to bf16 as MFMA operands only.
+ * bias_scatter: dtable[t][h] += sum of dense[h][e] over the entries e of index [SS] (int32) equal to t, in ascending order.
+ * Refused before any launch: window^2 > 64, a window that does not divide res, a shift outside [0, window) or on a window
+ * that spans the grid, T > 32, buffers that are not 16-byte aligned, a short workspace.
+ * ------------------------------------------------------------------------------------------ */
+int aim_swin_win_attn_fwd(const aim_bf16* qkv, const float* bias, aim_bf16* out, float* lse, int frames, int res, int H, int window,
+                          int shift, void* stream);
+int aim_swin_win_attn_bwd(const aim_bf16* qkv, const float* bias, const aim_bf16* dout, const float* lse,
+                          aim_bf16* dqkv, float* dbias, int frames, int res, int H, int window, int shift, float* workspace,
+                          int64_t workspace_bytes, void* stream);
+int aim_swin_tattn_fwd(const aim_bf16* qkv, const float* bias, aim_bf16* out, float* lse, int B, int T, int L, int H, void* stream);
+int aim_swin_tattn_bwd(const aim_bf16* qkv, const float* bias, const aim_bf16* dout, const float* lse,
+                       aim_bf16* dqkv, float* dbias, int B, int T, int L, int H, float* workspace, int64_t workspace_bytes,
+                       void* stream);
+int64_t aim_swin_attn_bwd_workspace_bytes(int sequences, int H, int S);
+int aim_swin_bias_scatter(const float* dense, const int* index, float* dtable, int H, int SS, int ntable, void* stream);
 
 #ifdef __cplusplus
 }
