@@ -1,10 +1,16 @@
-"""Every call form of the attention kernels (aim_attn_fwd, aim_attn_fwd_fp8, aim_attn_bwd, aim_cls_attn_fwd/bwd,
-aim_tattn_fwd/bwd), float64 closed-form references of their values and gradients, and bounds derived from the kernels'
-rounding points.
+"""Every call form of the attention kernels (aim_attn_fwd, aim_attn_fwd_fp8, aim_attn_bwd, aim_attn_fwd_cls / aim_attn_bwd_cls,
+aim_cls_attn_fwd/bwd, aim_tattn_fwd/bwd, aim_tattn_fwd_infer), float64 closed-form references of their values and gradients,
+and bounds derived from the kernels' rounding points.
 
-A plain module (no fixtures): `test_attn_routes_gpu.py` runs every case on every route, one child process per route
-(`python attn_cases.py ROUTE OUT.json`; the switches are read once per process), and `test_attn_cases_cpu.py` proves on the
-CPU that the bounds accept an emulation of the kernels' arithmetic and reject the bugs they are meant to catch.
+A plain module (no fixtures): `test_attn_routes_gpu.py` runs `route_cases()` on every route, one child process per route
+(`python attn_cases.py ROUTE OUT.json`; the switches are read once per process), `test_attn_lengths_gpu.py` runs
+`length_cases()` -- kernels that no route switch reaches, at every length they accept -- in one child and the inference
+forms of tattn once more in a child with AIM_TATTN_LDS16=0, and `test_attn_cases_cpu.py` proves on the CPU that the bounds
+accept an emulation of the kernels' arithmetic and reject the bugs they are meant to catch.
+
+Kinds.  `spatial`: aim_attn_fwd / _fp8 / aim_attn_bwd.  `clsq`: the class query of the last block, aim_attn_fwd_cls /
+aim_attn_bwd_cls (compact out, dO [BT, D] and lse [BT, H]; dO is zero outside the class rows, which is the situation they
+are built for).  `cls`: the temporal class-token kernels aim_cls_attn_*.  `tattn`: aim_tattn_*.
 
 Routes.  `default`; `xt0` (AIM_ATTN_PIPE_XT=0: the left-over queries get a tick of their own); `two` (AIM_ATTN_BWD_PIPE=0:
 the two-kernel backward at every N); `grid1`, `grid3` (AIM_ATTN_PIPE_GRID: one persistent workgroup walks every item /
@@ -37,10 +43,20 @@ Bounds of the spatial kernels, from the rounding points of csrc/attn_fwd.hip and
       eDS = U8 |dS| + (1 + U8) p (rp |dP - delta| + edP + edelta) + 2 u |dS|
       |dQ' - dQ| <= U8 |dQ| + (1 + U8) (sum_j eDS |k_j| + 2 N u sum_j |dS||k_j|) / 8        (dK alike, over the queries)
       |dV' - dV| <= U8 |dV| + (1 + U8) (sum_i ePb |dO_i| + 2 N u sum_i p |dO_i|)
+clsq: the spatial references and bounds above with a dO that is zero outside the class rows, restricted to query row 0 for
+    out, lse and dq and taken over every key for dk and dv.  The kernels' arithmetic for that query is the full kernels' (the
+    forward is the full kernel's first query tile; the backward runs the dq kernel's key-pair step on a tile whose other
+    fifteen queries are zero, and a key's dK = bf16(dS) q / 8, dV = bf16(p) dO are single exact products where the matrix
+    kernels hold fp32 sums of one non-zero term), so no rounding point is added and the bounds carry over unchanged.
 cls_attn / tattn keep fp32 probabilities (sequence T <= 32): z is an fp32 sum of 64 products, expf and one division:
       ep = p (2 . 64 u sum |q||k| / 8 . 2 + (T + 16) u);   out: U8 |O| + sum ep |v| + 2 T u A
     the backward takes the probabilities it is given (fp32 of the float64 ones, or the forward kernel's) and stays in fp32
     up to the one bf16 rounding of dq, dk, dv (cls_attn non-compact: of dqkv + d).
+aim_tattn_fwd_infer: the bf16 form has the bits of aim_tattn_fwd's `out` (itself held to float64 above); every byte of the
+    fp8 form is the e4m3 cast of the float64 result or its neighbour on the grid, and over all T of one (geometry, family)
+    at most 1e-3 of the bytes are neighbours (test_aim_fp8_gpu.py's cap; its argument: an fp32 sum over T <= 32 terms errs by
+    ~2e-6 relative and e4m3's rounding boundaries lie 2^-4 .. 2^-3 apart, so ~6e-5 of the values may flip).  Pooled because
+    the smallest cases have fewer than 1000 bytes, where the cap would allow no neighbour at all.
 """
 import json
 import math
@@ -52,6 +68,7 @@ from typing import Dict, Optional
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+sys.path.append(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))          # the repository root: oracle, aim_amd
 from gemm_cases import U8, U24, _digest, _pad_intact, _padded, ratio  # noqa: E402
 
 BF16, F32, F64, FP8 = torch.bfloat16, torch.float32, torch.float64, torch.float8_e4m3fn
@@ -68,12 +85,22 @@ PRODUCT_BT = (1, 2, 9)
 SWEEP_BT, SWEEP_H = 2, 2
 FAMILY_STRIDE = 7                      # the other families on every 7th N of the sweep (all residues mod 32 and mod 64)
 SMALL_SHAPES = ((8, 8, 197, 12), (2, 32, 257, 16), (3, 1, 197, 12), (1, 31, 5, 2), (2, 16, 197, 12))    # B, T, N, H
+CLSQ_SHAPES = ((16, 197, 12), (8, 257, 16), (4, 5, 2), (1, 288, 1), (3, 64, 1))                         # BT, N, H
+TMAX = 32
+# B, N, H of the sweep over T = 1 .. 32.  tattn runs one wave per (b, n, h) item, 4 waves per workgroup up to T = 16 and 2
+# above: 3 and 30 items leave a partial last workgroup at 4 waves (3 % 4, 30 % 4) and at 2 (3 % 2).  cls_attn runs one
+# 64-thread workgroup per (b, h) at every T: it has one wave count and no partial workgroup.
+SWEEP_GEOMS = ((1, 3, 1), (2, 5, 3))
+LENGTH_MODES = ("lengths", "lds32")          # children of test_attn_lengths_gpu.py
+LENGTH_ENV = {"lengths": {}, "lds32": {"AIM_TATTN_LDS16": "0"}}
+INFER_CAP = 1e-3                             # share of fp8 bytes that may be the neighbour of the float64 cast, per pool
+SAT_T = (17, 32)                             # |v| = 600 saturates to +-448 on either side of the 4 / 2 wave switch
 
 
 @dataclass(frozen=True)
 class Case:
     name: str
-    kind: str                 # spatial | cls | tattn
+    kind: str                 # spatial | clsq | cls | tattn
     BT: int
     N: int
     H: int
@@ -83,9 +110,16 @@ class Case:
     T: int = 0
     alone: bool = False       # spatial: every frame also launched alone, must give the same bits
     poison: bool = False      # spatial: the frame / head independence case (BT = 3)
+    sweep: bool = False       # cls / tattn: a case of the sweep over T (tattn: also run through aim_tattn_fwd_infer)
 
 
-def cases():
+def tattn_wpb(T: int) -> int:
+    """Mirror of csrc/tattn.hip: waves (items) per workgroup of aim_tattn_fwd / _infer / _bwd"""
+    return 4 if T <= 16 else 2
+
+
+def route_cases():
+    """what every route of the spatial backward runs (test_attn_routes_gpu.py)"""
     out, seed = [], 1000
     for N, H in PRODUCT:
         for BT in PRODUCT_BT:
@@ -109,6 +143,31 @@ def cases():
                 out.append(Case(f"{kind}/B{B}T{T}N{N}H{H}/{fam}", kind, B * T, N, H, fam, seed, B=B, T=T))
                 seed += 1
     return out
+
+
+def length_cases():
+    """the kernels no route switch reaches, at every length they accept (test_attn_lengths_gpu.py)"""
+    out, seed = [], 5000
+    for BT, N, H in CLSQ_SHAPES:
+        for fam in FAMILIES:
+            out.append(Case(f"clsq/{N}x{H}/BT{BT}/{fam}", "clsq", BT, N, H, fam, seed))
+            seed += 1
+    for N in range(1, NMAX + 1):
+        fams = FAMILIES if N % FAMILY_STRIDE == 1 else ("unit",)
+        for fam in fams:
+            out.append(Case(f"clsq/sweep/N{N}/{fam}", "clsq", SWEEP_BT, N, SWEEP_H, fam, seed))
+            seed += 1
+    for B, N, H in SWEEP_GEOMS:
+        for T in range(1, TMAX + 1):
+            for kind in ("cls", "tattn"):
+                for fam in ("unit", "peaked"):
+                    out.append(Case(f"{kind}/sweep/B{B}N{N}H{H}/T{T}/{fam}", kind, B * T, N, H, fam, seed, B=B, T=T, sweep=True))
+                    seed += 1
+    return out
+
+
+def cases():
+    return route_cases() + length_cases()
 
 
 def bwd_plan(N: int, route: str):
@@ -147,7 +206,7 @@ def make_inputs(case: Case) -> Dict[str, torch.Tensor]:
     BT, N, H, fam = case.BT, case.N, case.H, case.family
     q, k, v = (torch.randn((BT, N, H, 64), generator=g) for _ in range(3))
     do = torch.randn((BT, N, H, 64), generator=g)
-    if case.kind != "spatial":
+    if case.kind in ("cls", "tattn"):
         sc = 2.5 if fam == "peaked" else 0.8
         q, k = q * sc, k * sc
     elif fam == "peaked":
@@ -318,6 +377,164 @@ def compare_spatial(case: Case, inp, got, form: str = "a") -> Dict[str, float]:
     fw, bw_a, bw_b = spatial_expected(case, inp)
     exp = dict(fw, **(bw_a if form == "a" else bw_b))
     return {k: ratio(got[k], *exp[k]) for k in got if k in exp}
+
+
+# ------------------------------------------------------------------ the class query of the last block (clsq) ---------------
+def clsq_inputs(case: Case) -> Dict[str, torch.Tensor]:
+    """make_inputs with dO zero outside the class rows; the kernels get the compact rows `do_cls` [BT, D]"""
+    inp = make_inputs(case)
+    D = case.H * 64
+    inp["do"].view(case.BT, case.N, D)[:, 1:] = 0
+    inp["do_cls"] = inp["do"].view(case.BT, case.N, D)[:, 0].contiguous()
+    return inp
+
+
+def clsq_expected(case: Case, inp):
+    """(reference, bound) of out, lse [query row 0] and of dq [row 0], dk, dv [every key] in both backward forms, and what
+    form (a) hands in: `_out_a` [BT, D] bf16, `_lse_a` [BT, H] f32"""
+    BT, N, H = case.BT, case.N, case.H
+    q, k, v = split(inp["qkv"], BT, N, H, 3)
+    do = split(inp["do"], BT, N, H)
+    fw = forward_ref(q, k, v)
+    o_a, l_a, eo, el = handed_in(fw)
+    row0 = lambda pair: (pair[0][:, :, 0], pair[1][:, :, 0])
+    exp = {"out": row0(fw["out"]), "lse": row0(fw["lse"])}
+    for form, (eo_, el_) in (("a", (eo, el)), ("b", (fw["out"][1], fw["lse"][1]))):
+        bw = backward_ref(q, k, v, do, fw, eo_, el_)
+        exp[f"dq@{form}"], exp[f"dk@{form}"], exp[f"dv@{form}"] = row0(bw["dq"]), bw["dk"], bw["dv"]
+    exp["_out_a"] = o_a[:, :, 0].reshape(BT, H * 64).contiguous()
+    exp["_lse_a"] = l_a[:, :, 0].contiguous()
+    return exp
+
+
+def compare_clsq(case: Case, exp, got, form: str) -> Dict[str, float]:
+    """worst error / bound of out [BT, H, 64], lse [BT, H] and dq, dk, dv [BT, H, N, 64] (those present in `got`)"""
+    r = {k: ratio(got[k], *exp[k]) for k in ("out", "lse") if k in got}
+    if "dq" in got:
+        r["dq"] = ratio(got["dq"][:, :, 0], *exp[f"dq@{form}"])
+        r["dk"] = ratio(got["dk"], *exp[f"dk@{form}"])
+        r["dv"] = ratio(got["dv"], *exp[f"dv@{form}"])
+    return r
+
+
+def clsq_exact(case: Case, got) -> Dict[str, bool]:
+    """the exact properties of one backward result: everything finite, every non-class dQ row zero, a zero_do head zero"""
+    dq, dk, dv = got["dq"], got["dk"], got["dv"]
+    res = {"finite": bool(all(torch.isfinite(t.float()).all() for t in (dq, dk, dv))),
+           "other_dq_zero": bool((dq[:, :, 1:] == 0).all())}
+    if case.family == "zero_do":
+        h = min(1, case.H - 1)
+        res["zero_head"] = bool(all((t[:, h] == 0).all() for t in (dq, dk, dv)))
+    return res
+
+
+CLSQ_MUTANTS = ("lse_transposed", "do_full_stride", "delta_next_head", "dk_no_eighth", "keys_past_64_unwritten",
+                "other_dq_untouched", "out_row_stride")
+
+
+def emulate_clsq(case: Case, inp, mut: Optional[str] = None, own: bool = False, exp=None):
+    """aim_attn_fwd_cls / aim_attn_bwd_cls restated in float64 with their rounding points: fp32 scores, exp2 against the max
+    (forward) or the lse handed in (backward), delta = dO . O as one fp32 dot, bf16 p and dS, dK = bf16(bf16(dS) q / 8) and
+    dV = bf16(bf16(p) dO) as single products, explicit zeros in every other dQ row.  `mut` inserts one defect
+    (CLSQ_MUTANTS); what a defect leaves unwritten keeps the NaN the buffers are filled with, what it reads outside the
+    compact dO is the NaN around a guarded input.  own: form (b).  -> out [BT, H, 64], lse [BT, H], dq, dk, dv [BT, H, N, 64],
+    spare_intact (of `out`, in gemm_cases._padded's layout)"""
+    BT, N, H = case.BT, case.N, case.H
+    D = H * 64
+    exp = exp or clsq_expected(case, inp)
+    q, k, v = split(inp["qkv"], BT, N, H, 3)
+    q0 = q[:, :, 0]
+    do0 = inp["do_cls"].double().reshape(BT, H, 64)
+    r32 = lambda t: t.to(F32).double()
+    r16 = lambda t: t.to(F32).to(BF16).double()
+    nan = float("nan")
+    z = r32(torch.einsum("bhd,bhnd->bhn", q0, k)) / 8
+    mx = z.amax(dim=-1, keepdim=True)
+    pu = r32(torch.exp(z - mx))
+    tot = pu.sum(dim=-1, keepdim=True)
+    lse = r32(mx + torch.log(r32(tot)))[..., 0]
+    out = r32(r32(torch.einsum("bhn,bhnd->bhd", r16(pu), v)) / tot).to(BF16)
+    spare_intact = True
+    if mut == "out_row_stride":                       # the forward stores frame bt's row at bt N instead of bt
+        n = BT * D
+        flat = torch.full((n + 8 + 3 * (n + 8),), nan, dtype=F64)
+        for bt in range(BT):
+            if (bt * N + 1) * D <= flat.numel():      # (past the buffer: nothing the test can look at)
+                flat[bt * N * D:(bt * N + 1) * D] = out[bt].double().reshape(D)
+        out, spare_intact = flat[:n].reshape(BT, H, 64).to(BF16), bool(torch.isnan(flat[n:]).all())
+    got = {"out": out, "lse": lse.to(F32), "spare_intact": spare_intact}
+    if own:
+        out_in, lse_in = out.double(), got["lse"].double()
+    else:
+        out_in, lse_in = exp["_out_a"].double().reshape(BT, H, 64), exp["_lse_a"].double()
+    if mut == "lse_transposed":                       # item (bt, h) reads element h BT + bt of the [BT, H] array
+        idx = torch.arange(H)[None, :] * BT + torch.arange(BT)[:, None]
+        lse_in = lse_in.reshape(-1)[idx]
+    if mut == "do_full_stride":                       # item (bt, h) reads row bt N of the [BT, D] array
+        rows = torch.arange(BT) * N
+        do0 = torch.where((rows < BT)[:, None, None], do0[rows.clamp_max(BT - 1)], torch.full_like(do0, nan))
+    delta = r32((do0 * out_in).sum(dim=-1, keepdim=True))
+    if mut == "delta_next_head":
+        delta = delta.roll(-1, dims=1)
+    pb = r32(torch.exp(z - lse_in[..., None]))
+    dP = r32(torch.einsum("bhd,bhnd->bhn", do0, v))
+    dsb, pbb = r16(pb * (dP - delta)), r16(pb)
+    dq = torch.zeros((BT, H, N, 64), dtype=F64)
+    dq[:, :, 0] = r32(torch.einsum("bhn,bhnd->bhd", dsb, k)) * 0.125
+    dk = r32(dsb[..., None] * q0[:, :, None, :]) * (1.0 if mut == "dk_no_eighth" else 0.125)
+    dv = r32(pbb[..., None] * do0[:, :, None, :])
+    if mut == "other_dq_untouched":
+        dq[:, :, 1:] = nan
+    if mut == "keys_past_64_unwritten":               # the write loop's second trip (j = tid >> 3; j < N; j += 64) never runs
+        dq[:, :, 64:], dk[:, :, 64:], dv[:, :, 64:] = nan, nan, nan
+    got.update(dq=dq.to(BF16), dk=dk.to(BF16), dv=dv.to(BF16))
+    return got
+
+
+# ------------------------------------------------------------------ aim_tattn_fwd_infer ------------------------------------
+def tattn_ref64(qkv, B, T, N, H):
+    """float64 attention over the frame axis of the bf16 values -> rows [B*T*N, D]"""
+    D = H * 64
+    x = qkv.double().reshape(B, T, N, 3, H, 64).permute(3, 0, 2, 4, 1, 5)      # [3, B, N, H, T, 64]
+    p = ((x[0] @ x[1].transpose(-1, -2)) / 8.0).softmax(-1)
+    return (p @ x[2]).permute(0, 3, 1, 2, 4).reshape(B * T * N, D)
+
+
+def e4m3_code(b):
+    """signed position of an e4m3 byte on its grid (+0 and -0 share position 0)"""
+    b = b.to(torch.int32)
+    mag = b & 0x7F
+    return torch.where(b >= 0x80, -mag, mag)
+
+
+def e4m3_bytes(x):
+    """the saturating e4m3 cast of a result (the oracle's q8 of its fp32 value) as bytes"""
+    from oracle import vit_clip_oracle as O
+    return O.q8(x.float()).to(FP8).view(torch.uint8)
+
+
+def tattn_infer_emulate(qkv, B, T, N, H):
+    """the arithmetic of aim_tattn_fwd_infer's fp8 form in fp32: scores as fp32 sums of exact bf16 products, fp32 softmax
+    (expf, one reciprocal), fp32 P.V over T terms, saturating e4m3 cast -> bytes [B*T*N, D]"""
+    D = H * 64
+    x = qkv.float().reshape(B, T, N, 3, H, 64).permute(3, 0, 2, 4, 1, 5)
+    z = (x[0] @ x[1].transpose(-1, -2)) * 0.125
+    e = torch.exp(z - z.amax(dim=-1, keepdim=True))
+    p = e * (1.0 / e.sum(dim=-1, keepdim=True))
+    return e4m3_bytes((p @ x[2]).permute(0, 3, 1, 2, 4).reshape(B * T * N, D))
+
+
+def infer_pool(case: Case) -> str:
+    return f"B{case.B}N{case.N}H{case.H}/{case.family}"
+
+
+def saturating_qkv(case: Case):
+    """every frame's v is +-600 (sign by column): the attention's average is +-600 whatever the weights -> qkv, wanted bytes"""
+    D = case.H * 64
+    qkv = make_inputs(case)["qkv"].float()
+    sign = torch.where(torch.arange(D) % 3 == 0, -1.0, 1.0)
+    qkv[:, 2 * D:] = 600.0 * sign
+    return qkv.to(BF16), torch.where(sign < 0, 0xFE, 0x7E).to(torch.uint8).expand(case.BT * case.N, D)
 
 
 # ------------------------------------------------------------------ float64 references and bounds: cls_attn / tattn --------
@@ -607,6 +824,102 @@ class Runner:
                 chk[f"dqkv@{form}"] = ratio(host[f"dqkv@{form}"], d, U8 * d.abs() + (1 + U8) * e)
         return rec
 
+    def clsq_all(self, qkv, do_cls, out_a, lse_a, BT, N, H):
+        """class-query forward, backward of form a (rounded float64 out / lse handed in) and of form b (the forward's own),
+        every output in a NaN-filled buffer -> views, buffers"""
+        D, dev, ops = H * 64, self.dev, self.ops
+        got, bufs = {}, {}
+
+        def new(name, n, dtype, shape):
+            vw, buf = _flat(n, dtype, dev)
+            got[name], bufs[name] = vw.view(shape), (buf, n)
+            return got[name]
+
+        out = new("out", BT * D, BF16, (BT, D))
+        lse = new("lse", BT * H, F32, (BT, H))
+        ops.attn_fwd_cls(qkv, out, lse, BT, N, H)
+        for form, o, l in (("a", out_a, lse_a), ("b", out, lse)):
+            dqkv = new(f"dqkv@{form}", BT * N * 3 * D, BF16, (BT * N, 3 * D))
+            ops.attn_bwd_cls(qkv, o, do_cls, l, dqkv, BT, N, H)
+        return got, bufs
+
+    def run_clsq(self, case: Case):
+        dev, BT, N, H = self.dev, case.BT, case.N, case.H
+        D = H * 64
+        inp = clsq_inputs(case)
+        exp = clsq_expected(case, inp)
+        qkv, do_cls = _guarded(inp["qkv"], dev), _guarded(inp["do_cls"], dev)
+        out_a, lse_a = _guarded(exp["_out_a"], dev), _guarded(exp["_lse_a"], dev)
+        got, bufs = self.clsq_all(qkv, do_cls, out_a, lse_a, BT, N, H)
+        again, _ = self.clsq_all(qkv, do_cls, out_a, lse_a, BT, N, H)
+        # row 0 of the full forward kernel on the same input
+        full_out = torch.empty((BT * N, D), dtype=BF16, device=dev)
+        full_lse = torch.empty((BT, H, N), dtype=F32, device=dev)
+        self.ops.attn_fwd(qkv, full_out, full_lse.view(-1), BT, N, H)
+        # NaN in the q part of every non-class row: nothing the class query's result depends on
+        poisoned = inp["qkv"].clone()
+        poisoned.view(BT, N, 3 * D)[:, 1:, :D] = float("nan")
+        pois, _ = self.clsq_all(_guarded(poisoned, dev), do_cls, out_a, lse_a, BT, N, H)
+        torch.cuda.synchronize()
+        rec = {"checks": {}, "pad": {}, "finite": {}, "hash": {}, "repeat": {}, "poison": {}}
+        bits = lambda t: t.view(_BITS[t.dtype])
+        for name in got:
+            rec["repeat"][name] = bool(torch.equal(bits(got[name]), bits(again[name])))
+            rec["poison"][name] = bool(torch.equal(bits(got[name]), bits(pois[name])))
+            rec["pad"][name] = _pad_intact(bufs[name][0], 1, bufs[name][1])
+            rec["finite"][name] = bool(torch.isfinite(got[name].float()).all())
+            rec["hash"][name] = _digest(bits(got[name]))
+        rec["row0_of_attn_fwd"] = bool(torch.equal(bits(got["out"]), bits(full_out.view(BT, N, D)[:, 0].contiguous()))
+                                       and torch.equal(bits(got["lse"]), bits(full_lse[:, :, 0].contiguous())))
+        host = {k_: t.cpu() for k_, t in got.items()}
+        fwd = {"out": host["out"].view(BT, H, 64), "lse": host["lse"]}
+        rec["checks"].update(compare_clsq(case, exp, fwd, "a"))
+        for form in "ab":
+            dq, dk, dv = split(host[f"dqkv@{form}"], BT, N, H, 3)
+            bwd = {"dq": dq, "dk": dk, "dv": dv}
+            rec["checks"].update({f"{k_}@{form}": r for k_, r in compare_clsq(case, exp, bwd, form).items()})
+            for k_, ok in clsq_exact(case, bwd).items():
+                rec[f"{k_}@{form}"] = ok
+        return rec
+
+    def run_infer(self, case: Case):
+        """aim_tattn_fwd_infer on a tattn sweep case under this process's LDS staging: the bf16 form against aim_tattn_fwd's
+        bits, the fp8 form byte by byte against the e4m3 cast of the float64 result"""
+        dev, ops = self.dev, self.ops
+        B, T, N, H, M = case.B, case.T, case.N, case.H, case.BT * case.N
+        D = H * 64
+        qkv_h = make_inputs(case)["qkv"]
+        qkv = _guarded(qkv_h, dev)
+        want16 = torch.empty((M, D), dtype=BF16, device=dev)
+        probs = torch.empty((B * N * H * T * T,), dtype=F32, device=dev)
+        ops.tattn_fwd(qkv, want16, probs, B, T, N, H)
+        rec = {"pad": {}, "repeat": {}}
+
+        def infer(src, fp8):
+            o16, buf = _flat(M * D // 2 if fp8 else M * D, BF16, dev)          # (the fp8 bytes inside a bf16 NaN buffer)
+            out = o16.view(torch.uint8).view(M, D) if fp8 else o16.view(M, D)
+            ops.tattn_fwd_infer(src, out, B, T, N, H)
+            return out, buf, o16.numel()
+
+        o16, b16, n16 = infer(qkv, False)
+        o8, b8, n8 = infer(qkv, True)
+        o16_2, _, _ = infer(qkv, False)
+        o8_2, _, _ = infer(qkv, True)
+        torch.cuda.synchronize()
+        rec["bf16_is_tattn_fwd"] = bool(torch.equal(o16.view(torch.int16), want16.view(torch.int16)))
+        rec["repeat"] = {"out": bool(torch.equal(o16.view(torch.int16), o16_2.view(torch.int16))), "out8": bool(torch.equal(o8, o8_2))}
+        rec["pad"] = {"out": _pad_intact(b16, 1, n16), "out8": _pad_intact(b8, 1, n8)}
+        got = o8.cpu()
+        step = (e4m3_code(got) - e4m3_code(e4m3_bytes(tattn_ref64(qkv_h, B, T, N, H)))).abs()
+        rec.update(bytes=got.numel(), neighbours=int((step == 1).sum()), farther=int((step > 1).sum()), hash8=_digest(got),
+                   pool=infer_pool(case))
+        if T in SAT_T and case.family == "unit":
+            sat, want = saturating_qkv(case)
+            s8, sb, sn = infer(_guarded(sat, dev), True)
+            torch.cuda.synchronize()
+            rec["saturates"] = bool(torch.equal(s8.cpu(), want)) and _pad_intact(sb, 1, sn)
+        return rec
+
     def run_large(self, BT, tag):
         """BT x 197 x 12 with the qkv buffer above 2^31 (2^32) bytes: float64 on the first two and last two frames, the bits of
         those frames against a four-frame launch, finiteness everywhere"""
@@ -677,7 +990,26 @@ class Runner:
                 out[name] = None
             except RuntimeError as e:
                 out[name] = str(e)
+        # the class-query kernels, through the library itself (a null pointer cannot pass ops): buffers large enough for the
+        # largest refused shape, outputs filled with NaN that must survive
+        import aim_amd
+        lib, st, n = aim_amd.load_library(), ops._stream(), NMAX + 1
+        qkv = torch.zeros((n, 192), dtype=BF16, device=dev)
+        o16, d16 = torch.zeros(64, dtype=BF16, device=dev), torch.zeros(64, dtype=BF16, device=dev)
+        l32 = torch.zeros(1, dtype=F32, device=dev)
+        outs = {"out_cls": torch.full((64,), float("nan"), dtype=BF16, device=dev),
+                "lse_cls": torch.full((1,), float("nan"), dtype=F32, device=dev),
+                "dqkv": torch.full((n, 192), float("nan"), dtype=BF16, device=dev)}
+        p = lambda t: t.data_ptr()
+        fwd = lambda BT, N, lse: lib.aim_attn_fwd_cls(p(qkv), p(outs["out_cls"]), lse, BT, N, 1, st)
+        bwd = lambda BT, N, lse: lib.aim_attn_bwd_cls(p(qkv), p(o16), p(d16), lse, p(outs["dqkv"]), BT, N, 1, st)
+        for kernel, f, lse in (("attn_fwd_cls", fwd, p(outs["lse_cls"])), ("attn_bwd_cls", bwd, p(l32))):
+            for tag, args in (("N=289", (1, n, lse)), ("N=0", (1, 0, lse)), ("BT=0", (0, 1, lse)), ("null lse_cls", (1, 1, None))):
+                rc = f(*args)
+                msg = lib.aim_last_error()
+                out[f"{kernel} {tag}"] = (msg.decode() if msg else "") if rc != 0 else None
         torch.cuda.synchronize()
+        self.refusals_untouched = {k: bool(torch.isnan(t).all()) for k, t in outs.items()}
         return out
 
 
@@ -689,9 +1021,24 @@ def main(argv):
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     res = {"route": route, "cus": cus, "cases": {}, "large": {}}
     run = Runner(ops, route, cus, dev)
+    if route in LENGTH_MODES:          # lengths: every length case, then the inference forms; lds32: the inference forms alone
+        assert (os.environ.get("AIM_TATTN_LDS16") == "0") == (route == "lds32"), "the staging switch does not match the mode"
+        res["infer"] = {}
+        with torch.no_grad():
+            res["refusals"] = run.refusals()
+            res["refusals_untouched"] = run.refusals_untouched
+            for case in length_cases():
+                if route == "lengths":
+                    res["cases"][case.name] = run.run_clsq(case) if case.kind == "clsq" else run.run_small(case)
+                if case.kind == "tattn":
+                    res["infer"][case.name] = run.run_infer(case)
+        with open(path, "w") as f:
+            json.dump(res, f)
+        return
     with torch.no_grad():
         res["refusals"] = run.refusals()
-        for case in cases():
+        res["refusals_untouched"] = run.refusals_untouched
+        for case in route_cases():
             res["cases"][case.name] = run.run_spatial(case) if case.kind == "spatial" else run.run_small(case)
         torch.cuda.empty_cache()
         res["large"]["2^31"] = run.run_large(2400, "2^31")

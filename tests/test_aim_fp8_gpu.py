@@ -6,7 +6,8 @@ the suite's parity record (``test_fp8_gpu._record``).
 Measured on MI355X, fp8_vs_emu8 / emu8_vs_emu16 (bound: ratio < 0.75) / fp8_vs_bf16 / bf16_vs_emu16:
   B16_L2  3.05e-2 / 5.59e-2 (ratio 0.55) / 5.55e-2 / 3.2e-3
   L14_L2  2.95e-2 / 5.20e-2 (ratio 0.57) / 5.42e-2 / 2.9e-3
-fp8 form of the kernel against float64: all 37 056 bytes of the four shapes equal, under either LDS staging.
+fp8 form of the kernel against float64: all 37 056 bytes of the four shapes equal, under either LDS staging (every T from
+1 to 32 under both stagings: test_attn_lengths_gpu.py).
 """
 import os
 import sys
@@ -19,6 +20,7 @@ from oracle import vit_clip_oracle as O
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import aim_fp8_emu as E  # noqa: E402
+from attn_cases import e4m3_code as _code, tattn_ref64 as _ref64  # noqa: E402  (shared with the sweep over every T)
 from test_fp8_gpu import _record  # noqa: E402  (the parity record that the ViT_CLIP fp8 tests append to)
 
 pytestmark = pytest.mark.gpu
@@ -49,21 +51,6 @@ def _guarded(M, D, dtype):
 
 def _guard_intact(buf, M, D, dtype):
     return bool((buf[M * D * dtype.itemsize:] == 0xA5).all())
-
-
-def _ref64(qkv, B, T, N, H):
-    """float64 attention over the frame axis of the bf16 values -> rows [B*T*N, D]"""
-    D = H * 64
-    x = qkv.double().reshape(B, T, N, 3, H, 64).permute(3, 0, 2, 4, 1, 5)      # [3, B, N, H, T, 64]
-    p = ((x[0] @ x[1].transpose(-1, -2)) / 8.0).softmax(-1)
-    return (p @ x[2]).permute(0, 3, 1, 2, 4).reshape(B * T * N, D)
-
-
-def _code(b):
-    """signed position of an e4m3 byte on its grid (+0 and -0 share position 0)"""
-    b = b.to(torch.int32)
-    mag = b & 0x7F
-    return torch.where(b >= 0x80, -mag, mag)
 
 
 @pytest.mark.parametrize("B,T,N,H", SHAPES)
