@@ -47,10 +47,18 @@ def test_case_list_covers_the_issue():
 
 
 def test_the_shift_module_keeps_its_own_boxes():
-    """handing the cut rule over is for the duration of a call"""
-    saved = WS.boxes
-    WC.box_rows(1, 4, 4, (2, 2, 2), (1, 1, 1))
-    assert WS.boxes is saved and WS.boxes is not WC.boxes
+    """the rule is an argument: calls into the cut table leave what the shift table returns as it was"""
+    case = min(WS.cases(), key=lambda c: c.B * c.T * c.N)          # the smallest shifted case
+    geom = (case.B, case.T, case.G, case.window, case.shift)
+    inp = WS.make_inputs(case)
+    rows, got = WS.box_rows(*geom), WS.emulate(case, inp, None, own=True)
+    cut = _by(0, "unit")
+    assert len(WC.box_rows(*geom)) != len(rows)                     # the cut rule groups this geometry otherwise
+    WC.boxes(*geom)
+    WC.compare(cut, _inp(cut), WC.emulate(cut, _inp(cut), "t_wraps", own=True), "b", _GROUPS[cut.name])
+    rows2, got2 = WS.box_rows(*geom), WS.emulate(case, inp, None, own=True)
+    assert len(rows) == len(rows2) and all(torch.equal(a, b) for a, b in zip(rows, rows2))
+    assert set(got) == set(got2) and all(torch.equal(got[k], got2[k]) for k in got)
     assert sorted(idx.shape[1] for idx in WS.box_rows(1, 4, 4, (2, 2, 2), (1, 1, 1))) == [2, 4, 8]
 
 
