@@ -6,6 +6,21 @@ A plain module in the manner of win_attn_cases.py: `test_swin_attn_gpu.py` runs 
 child process for the whole list) and `test_swin_attn_cases_cpu.py` proves on the CPU that the bounds accept an emulation of
 the kernels' arithmetic and reject the defects they are meant to catch (MUTANTS).
 
+Two more lists run in a second child (`python swin_attn_cases.py --sweep OUT.json`, tests/test_swin_attn_sweep_gpu.py) under the
+same references and bounds, which do not depend on how the backward splits its work:
+  chunk_cases()  the backward's walk over several sequences per workgroup.  `chunks` restates the kernels' chunks_of; every case
+                 of `cases()` has one sequence per workgroup, these have 3 (windows of 49, 64 and 16 tokens, T' = 5 and 32) and 8,
+                 a short last chunk, and a walk length coprime to the windows of a frame, so one workgroup meets different
+                 region patterns in turn.  The second launch replaces one mid-chunk sequence: no other row may change.
+  sweep_cases()  every T' from 1 to 32 and every window side from 1 to 8 at every shift, three more input families (bias_big:
+                 |bias| up to 40; cross_hot: every masked score 126 or more above every allowed one; zero_do: one head of dO
+                 zero, that head's gradients exactly zero), and on the shifts 1 and w - 1 the tokens that are alone in their
+                 region: out = v, dv = dO, dq = dk = 0 bit for bit, and nothing of them in the bias gradients.
+The child also asks for the refusal of null and misaligned pointers and of a short or missing workspace, checks the floats
+behind a workspace of exactly the reported size, and adds a scatter onto a non-zero table.  NEW_MUTANTS are the defects of
+that ground: a stale region table, a bias-gradient sum restarted per sequence, a dropped short chunk, a max over masked keys, the
+reference's -100 in place of the weight 0, a scaled bias gradient.
+
 Geometry.  Window cases: `frames` frames of a res x res grid, frame-major rows f res^2 + y res + x.  Token i = (iy, ix) of
 window (wy, wx) has ROLLED coordinates (wy w + iy, wx w + ix) and lies at row ((wy w + iy + s) mod res, (wx w + ix + s) mod res):
 the reference's roll by -s, window_partition, window_reverse and roll back.  With s > 0 each rolled axis has the regions
@@ -65,6 +80,18 @@ WIN_SHAPES = ((2, 14, 7, 3, 1),      # 1 / 2 / 2 / 4-region windows
 # B, T', L, heads
 T_SHAPES = ((1, 1, 5, 1), (2, 2, 49, 2), (1, 3, 10, 1), (1, 16, 64, 4), (1, 32, 8, 1))
 FAMILIES = ("unit", "peaked")
+# families of the new case lists only (chunk_cases, sweep_cases); `cases()` keeps FAMILIES
+NEW_FAMILIES = ("bias_big", "cross_hot", "zero_do")
+ALL_FAMILIES = FAMILIES + NEW_FAMILIES
+BIAS_BIG = 40.0                      # bias_big: the largest |bias|
+HOT_Q, HOT_K = 16.0, 48.0            # cross_hot: exact in bf16; c HOT_Q HOT_K = 135.8 on a pair of different regions
+# backward with per >= 2 sequences per workgroup.  windows (frames, res, w, s, H), temporal (B, T', L, H)
+CHUNK_WIN = ((35, 14, 7, 3, 16),     # (a) CAP 64, S 49: nseq 140, per 3, 47 chunks, the last one of 2
+             (35, 16, 8, 4, 16),     # (b) CAP 64, S 64
+             (35, 8, 4, 2, 16))      # (c) CAP 32, S 16
+CHUNK_T = ((1, 5, 140, 16),          # (d) a partial wave: nseq 140, per 3, 47 chunks, the last one of 2
+           (1, 32, 70, 32))          #     T' 32: nseq 70, per 3, 24 chunks, the last one of 1
+CHUNK_DEEP = (227, 6, 2, 1, 4)       # (e) nseq 2043, per 8, 256 chunks, the last one of 3; s = w - 1: one-key regions
 SENTINEL = -7.0
 
 
@@ -116,6 +143,52 @@ def cases():
     return out
 
 
+def chunks(nseq, H):
+    """chunks_of of csrc/swin_attn.hip restated -> (nchunks, per): the backward grid is (nchunks, H) and a workgroup walks
+    the `per` sequences [chunk per, min((chunk + 1) per, nseq)) in ascending order"""
+    n = min(nseq, (1024 + H - 1) // H)
+    per = (nseq + n - 1) // n
+    return (nseq + per - 1) // per, per
+
+
+def chunk_cases():
+    """the backward's walk over several sequences per workgroup (per >= 3; per >= 8 in the deep case), both FAMILIES"""
+    out, seed = [], 7100
+    for kind, shapes in (("win", CHUNK_WIN), ("t", CHUNK_T), ("win", (CHUNK_DEEP,))):
+        for d in shapes:
+            for fam in FAMILIES:
+                tag = f"f{d[0]}r{d[1]}w{d[2]}s{d[3]}h{d[4]}" if kind == "win" else f"B{d[0]}T{d[1]}L{d[2]}h{d[3]}"
+                out.append(Case(f"chunk/{kind}/{tag}/{fam}", kind, d, fam, seed))
+                seed += 1
+    return out
+
+
+def sweep_families(kind, dims):
+    if kind == "t":
+        return tuple(f for f in ALL_FAMILIES if f != "cross_hot") if dims[1] % 7 == 0 else ("unit",)
+    w, s = dims[2], dims[3]
+    return ALL_FAMILIES if w >= 5 and s in (1, w - 1) else ("unit",)
+
+
+def sweep_cases():
+    """every T' from 1 to 32 (B 2, L 5, H 2) and every window side from 1 to 8 at every shift (2 frames of a 3 w x 3 w grid,
+    H 2: interior, edge and corner windows); `unit` everywhere, ALL_FAMILIES on every seventh T' (cross_hot needs a mask:
+    windows only) and on w in 5..8 with s in {1, w - 1}"""
+    out, seed = [], 7200
+    for T in range(1, 33):
+        d = (2, T, 5, 2)
+        for fam in sweep_families("t", d):
+            out.append(Case(f"sweep/t/T{T}/{fam}", "t", d, fam, seed))
+            seed += 1
+    for w in range(1, 9):
+        for s in range(w):
+            d = (2, 3 * w, w, s, 2)
+            for fam in sweep_families("win", d):
+                out.append(Case(f"sweep/win/w{w}s{s}/{fam}", "win", d, fam, seed))
+                seed += 1
+    return out
+
+
 # ------------------------------------------------------------------ geometry and bias ---------------------------------------
 def _regions(c, res, w, s):
     return torch.where(c < res - w, 0, torch.where(c < res - s, 1, 2)) if s else torch.zeros_like(c)
@@ -142,7 +215,28 @@ def geometry(case: Case, mut: Optional[str] = None):
     allow = reg[:, :, None] == reg[:, None, :]
     if mut == "no_mask":
         allow = torch.ones_like(allow)
+    if mut == "stale_region":      # the region table of the chunk's first sequence kept for all of its sequences
+        per = chunks(case.nseq, case.H)[1]
+        allow = allow[torch.arange(case.nseq) // per * per]
     return idx, allow
+
+
+def row_regions(case: Case):
+    """-> [rows] the mask region of every row of a window case (0 where nothing is masked)"""
+    frames, res, w, s, _ = case.dims
+    idx, _ = geometry(case)
+    nw = res // w
+    _, wy, wx, iy, ix = torch.meshgrid(torch.arange(frames), torch.arange(nw), torch.arange(nw), torch.arange(w), torch.arange(w),
+                                       indexing="ij")
+    reg = _regions(wy * w + iy, res, w, s) * 3 + _regions(wx * w + ix, res, w, s)
+    out = torch.zeros(case.rows, dtype=torch.long)
+    out[idx.reshape(-1)] = reg.reshape(-1)
+    return out
+
+
+def lone_tokens(case: Case):
+    """-> [nseq, S] bool: the tokens that are alone in their mask region (a one-key softmax inside a masked window)"""
+    return geometry(case)[1].sum(dim=-1) == 1
 
 
 def rolled_geometry(frames, res, w, s):
@@ -206,7 +300,29 @@ def make_inputs(case: Case) -> Dict[str, torch.Tensor]:
     if case.family == "peaked":
         q, k = q * 2.5, k * 2.5
     table = (0.75 * torch.randn((case.ntable, H), generator=g)).to(F32)
+    if case.family == "bias_big":        # the max and the lse come from the bias, not from q k
+        table = (table * (BIAS_BIG / float(table.abs().amax()))).to(F32)
+    elif case.family == "cross_hot":
+        # The first nine features hold a region one-hot: HOT_Q e_r in q, HOT_K (1 - e_r) in k, so c q.k gets exactly 0 from
+        # them on a pair of one region and c HOT_Q HOT_K = 135.8 on a pair of different regions: every masked score is far
+        # above every allowed one.  The float64 reference masks with -inf and never sees them.  (At +60 an fp32 kernel
+        # that took its max over the masked keys, or masked with the reference's -100, would still pass: e^-60 is a
+        # normal fp32 number and e^(60 - 100) is below every bound.  The gain has to exceed 100 + the spread of the scores
+        # for the -100 mask and 2^-149 for the max, hence 135.8.)  On such inputs the reference project's -100 mask
+        # differs from the weight 0 BY DESIGN: this family tests the kernels' documented contract only.
+        assert case.kind == "win" and case.dims[3] > 0, "cross_hot needs a shifted window case"
+        hot = torch.nn.functional.one_hot(row_regions(case), 9).to(q.dtype)[:, None, :]
+        q, k = q.view(M, H, HD), k.view(M, H, HD)
+        q[:, :, :9] = HOT_Q * hot
+        k[:, :, :9] = HOT_K * (1.0 - hot)
+        q, k = q.reshape(M, H * HD), k.reshape(M, H * HD)
+    elif case.family == "zero_do":       # dO = 0 for one head: its dq, dk, dv and its bias gradients are exactly zero
+        do.view(M, H, HD)[:, zero_head(case)] = 0.0
     return {"qkv": torch.cat([q, k, v], dim=1).to(BF16), "do": do.to(BF16), "table": table}
+
+
+def zero_head(case: Case):
+    return min(1, case.H - 1)
 
 
 def gather(x, idx, H, parts=1):
@@ -281,6 +397,8 @@ def expected(case: Case, inp):
 
 
 MUTANTS = ("bias_T", "no_mask", "shift_sign", "swap_hw", "t_neg")
+# defects of the walk over several sequences per workgroup, of the mask's weight 0 and of the bias gradient's scale
+NEW_MUTANTS = ("stale_region", "db_last_only", "drop_ragged_chunk", "max_before_mask", "penalty_mask", "dbias_scaled")
 
 
 def emulate(case: Case, inp, mut: Optional[str] = None):
@@ -297,9 +415,12 @@ def emulate(case: Case, inp, mut: Optional[str] = None):
     r16 = lambda t: t.to(F32).to(BF16).double()
     al = allow[:, None]
     ninf = torch.full((), -math.inf, dtype=F64)
-    x = torch.where(al, r32(r32(q @ k.transpose(-1, -2)) * SCALE + bias), ninf)
-    mx = x.amax(dim=-1, keepdim=True)
-    pu = r32(torch.exp(x - mx))
+    xa = r32(r32(q @ k.transpose(-1, -2)) * SCALE + bias)
+    if mut == "penalty_mask":          # the reference's -100 instead of the weight 0
+        xa, al = torch.where(al, xa, r32(xa - 100.0)), torch.ones_like(al)
+    x = torch.where(al, xa, ninf)
+    mx = (xa if mut == "max_before_mask" else x).amax(dim=-1, keepdim=True)
+    pu = r32(torch.exp(x - mx))        # (fp32: below 2^-149 it is 0)
     tot = r32(pu.sum(dim=-1, keepdim=True))
     lse = r32(mx + torch.log(tot))
     out = r16(r32(r16(pu) @ v) / tot)
@@ -311,7 +432,20 @@ def emulate(case: Case, inp, mut: Optional[str] = None):
     dq = r32(dsb @ k) * SCALE
     dk = r32(dsb.transpose(-1, -2) @ q) * SCALE
     dv = r32(r16(pb).transpose(-1, -2) @ do)
-    dB = r32(ds32.sum(dim=0))
+    # the two stages of the bias gradient: a workgroup's sum over the sequences of its chunk, then the sum over the chunks
+    n = idx.shape[0]
+    nch, per = chunks(n, H)
+    dsc = torch.cat([ds32, torch.zeros((nch * per - n, H, S, S), dtype=F64)]).view(nch, per, H, S, S)
+    if mut == "db_last_only":          # the sum restarted at every sequence: the chunk's last sequence alone
+        last = torch.tensor([min((c + 1) * per, n) - 1 - c * per for c in range(nch)])
+        partial = dsc[torch.arange(nch), last]
+    else:
+        partial = r32(dsc.sum(dim=1))
+    if mut == "drop_ragged_chunk" and n % per:
+        partial = partial[:-1]
+    dB = r32(partial.sum(dim=0))
+    if mut == "dbias_scaled":
+        dB = r32(dB * SCALE)
     return {"out": scatter(out.to(BF16), idx, M), "dqkv": torch.cat([scatter(t.to(BF16), idx, M) for t in (dq, dk, dv)], dim=1),
             "lse": lse[..., 0].to(F32), "dbias": dB.to(F32), "dtable": fold(dB, bias_index(case, mut), case.ntable).to(F32)}
 
@@ -378,7 +512,7 @@ class Runner:
         got["dqkv_nobias"] = dq2
         return got, bufs
 
-    def run_case(self, case: Case):
+    def run_case(self, case: Case, extras=False):
         inp = make_inputs(case)
         got, bufs = self.launch(case, inp)
         again, _ = self.launch(case, inp)
@@ -397,7 +531,64 @@ class Runner:
         for name, t in host.items():
             rec["finite"][name] = bool(torch.isfinite(t.float()).all())
         rec["checks"] = compare(case, inp, host)
+        if extras:
+            self.exact_properties(case, inp, got, host, rec)
         return rec
+
+    # ---- the exact properties of the new case lists
+    def _other_rows_keep_their_bits(self, case, got, got2, rows):
+        """`rows` of the inputs were replaced in the second launch: every other row of out and dqkv has the same bits"""
+        keep = torch.ones(case.rows, dtype=torch.bool)
+        keep[rows] = False
+        keep = keep.to(self.dev)
+        return {name: bool(torch.equal(_bits(got[name])[keep], _bits(got2[name])[keep])) for name in ("out", "dqkv", "dqkv_nobias")}
+
+    def _replaced(self, case, inp, rows):
+        g = torch.Generator().manual_seed(case.seed + 100000)
+        qkv, do = inp["qkv"].clone(), inp["do"].clone()
+        qkv[rows] = (1.5 * torch.randn((rows.numel(), qkv.shape[1]), generator=g)).to(BF16)
+        do[rows] = (1.5 * torch.randn((rows.numel(), do.shape[1]), generator=g)).to(BF16)
+        return {"qkv": qkv, "do": do, "table": inp["table"]}
+
+    def exact_properties(self, case: Case, inp, got, host, rec):
+        H, S, C = case.H, case.S, case.H * HD
+        idx, _ = geometry(case)
+        nch, per = chunks(case.nseq, H)
+        rec["workspace_bytes"] = [int(self.ops.load_library().aim_swin_attn_bwd_workspace_bytes(case.nseq, H, S)), nch * H * S * S * 4]
+        if case.family == "zero_do":
+            cols = slice(zero_head(case) * HD, (zero_head(case) + 1) * HD)
+            d = host["dqkv"].view(case.rows, 3, C)
+            rec["zero_head"] = {"dq": not d[:, 0, cols].any(), "dk": not d[:, 1, cols].any(), "dv": not d[:, 2, cols].any(),
+                                "dbias": not host["dbias"][zero_head(case)].any(), "dtable": not host["dtable"][:, zero_head(case)].any(),
+                                "other_heads_live": bool(host["dbias"].any()) or H == 1}
+        if case.kind == "win" and case.dims[2] > 1 and case.dims[3] in (1, case.dims[2] - 1):
+            # a token alone in its region: p = 1, so out = v, dv = dO, dq = dk = 0, bit for bit, and dS = 0: nothing of it
+            # reaches the bias gradient -- with its q, k, v and dO rows replaced the dense gradient keeps all its bits
+            rows = idx[lone_tokens(case)]
+            qkv, do, d = inp["qkv"].view(case.rows, 3, C), inp["do"], host["dqkv"].view(case.rows, 3, C)
+            got2, _ = self.launch(case, self._replaced(case, inp, rows))
+            torch.cuda.synchronize()
+            others = self._other_rows_keep_their_bits(case, got, got2, rows)
+            rec["one_key"] = {"tokens": int(rows.numel()), "out_is_v": bool(torch.equal(_bits(host["out"][rows]), _bits(qkv[rows, 2]))),
+                              "dv_is_do": bool(torch.equal(_bits(d[rows, 2]), _bits(do[rows]))),
+                              "dq_zero": not d[rows, 0].any(), "dk_zero": not d[rows, 1].any(),
+                              "dbias_same_bits_with_the_token_replaced": bool(torch.equal(_bits(got["dbias"]), _bits(got2["dbias"]))),
+                              "dtable_same_bits_with_the_token_replaced": bool(torch.equal(_bits(got["dtable"]), _bits(got2["dtable"]))),
+                              "replaced_rows_differ": not torch.equal(_bits(got["out"])[rows.to(self.dev)], _bits(got2["out"])[rows.to(self.dev)]),
+                              **{f"other_rows_{k}": v for k, v in others.items()}}
+        if per > 1:
+            # no leak between the sequences of one workgroup: the rows of one mid-chunk sequence replaced, every other
+            # sequence's out, lse and dqkv rows keep their bits
+            seq = (nch // 2) * per + 1
+            assert seq % per == 1 and seq + 1 < min((nch // 2 + 1) * per, case.nseq)
+            got2, _ = self.launch(case, self._replaced(case, inp, idx[seq]))
+            torch.cuda.synchronize()
+            sk = torch.ones(case.nseq, dtype=torch.bool, device=self.dev)
+            sk[seq] = False
+            rec["no_leak"] = {"sequence": seq, "chunk": nch // 2, "per": per,
+                              "lse2": bool(torch.equal(_bits(got["lse2"])[sk], _bits(got2["lse2"])[sk])),
+                              "replaced_sequence_differs": not torch.equal(_bits(got["lse2"])[seq], _bits(got2["lse2"])[seq]),
+                              **self._other_rows_keep_their_bits(case, got, got2, idx[seq])}
 
     def refusals(self):
         """geometry outside the limits: an error through aim_last_error and nothing written (the buffers are far too small for
@@ -424,14 +615,115 @@ class Runner:
                 out[name] = {"fwd": msg_f, "bwd": msg_b, "nothing_written": intact}
         return out
 
+    def _entry_buffers(self, case: Case):
+        """correctly sized buffers of one case, each followed by 64 spare elements, all filled with SENTINEL"""
+        H, S, M, C = case.H, case.S, case.rows, case.H * HD
+        nbytes = int(self.ops.load_library().aim_swin_attn_bwd_workspace_bytes(case.nseq, H, S))
+        sizes = {"qkv": (M * 3 * C, BF16), "out": (M * C, BF16), "dout": (M * C, BF16), "dqkv": (M * 3 * C, BF16), "bias": (H * S * S, F32),
+                 "lse": (case.nseq * H * cap(S), F32), "dbias": (H * S * S, F32), "workspace": (nbytes // 4, F32)}
+        return {k: torch.full((n + 64,), SENTINEL, dtype=dt, device=self.dev) for k, (n, dt) in sizes.items()}, nbytes
+
+    def _call(self, lib, case: Case, which, ptr, nbytes, dbias=True):
+        import ctypes
+        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        geom = (case.dims[0], case.dims[1], case.H, case.dims[2], case.dims[3]) if case.kind == "win" else case.dims
+        name = ("aim_swin_win_attn_" if case.kind == "win" else "aim_swin_tattn_") + which
+        if which == "fwd":
+            rc = getattr(lib, name)(ptr["qkv"], ptr["bias"], ptr["out"], ptr["lse"], *geom, st)
+        else:
+            rc = getattr(lib, name)(ptr["qkv"], ptr["bias"], ptr["dout"], ptr["lse"], ptr["dqkv"], ptr["dbias"] if dbias else None,
+                                    *geom, ptr["workspace"], nbytes, st)
+        return rc, (lib.aim_last_error().decode() if rc else None)
+
+    def pointer_refusals(self):
+        """null pointers, bf16 pointers off by 2 bytes and a short or missing workspace, on every entry that takes them: a
+        non-zero return, a message and nothing written.  The buffers have the call's true sizes and 64 spare elements, so
+        a pointer off by 2 bytes stays inside its buffer."""
+        lib, out = self.ops.load_library(), {}
+        for case in (Case("r", "win", (1, 8, 4, 2, 1)), Case("r", "t", (1, 4, 4, 1))):
+            bufs, nbytes = self._entry_buffers(case)
+            good = {k: (t.data_ptr() or None) for k, t in bufs.items()}
+            forms = {"fwd": [(f"null {k}", {k: None}, nbytes) for k in ("qkv", "bias", "out", "lse")] +
+                            [(f"{k} off by 2 bytes", {k: good[k] + 2}, nbytes) for k in ("qkv", "out")],
+                     "bwd": [(f"null {k}", {k: None}, nbytes) for k in ("qkv", "bias", "dout", "lse", "dqkv")] +
+                            [(f"{k} off by 2 bytes", {k: good[k] + 2}, nbytes) for k in ("qkv", "dout", "dqkv")] +
+                            [("workspace 4 bytes short", {}, nbytes - 4), ("null workspace", {"workspace": None}, nbytes)]}
+            for which, table in forms.items():
+                for name, change, nb in table:
+                    rc, msg = self._call(lib, case, which, {**good, **change}, nb)
+                    torch.cuda.synchronize()
+                    intact = all(bool((t == SENTINEL).all()) for t in bufs.values())
+                    out[f"{'swin_win_attn_' if case.kind == 'win' else 'swin_tattn_'}{which}: {name}"] = \
+                        {"rc": rc, "message": msg, "nothing_written": intact}
+        return out
+
+    def workspace_guard(self, case: Case):
+        """the backward called directly with a workspace of exactly the reported size: the 64 floats behind it are intact,
+        and the bias gradient has the bits that ops' own call gives"""
+        lib = self.ops.load_library()
+        inp = make_inputs(case)
+        got, _ = self.launch(case, inp)
+        bufs, nbytes = self._entry_buffers(case)
+        for k, t in (("qkv", inp["qkv"]), ("dout", inp["do"]), ("bias", dense_bias(inp["table"], bias_index(case), case.S)), ("lse", got["lse2"])):
+            bufs[k][:t.numel()] = t.reshape(-1).to(self.dev)
+        rc, msg = self._call(lib, case, "bwd", {k: t.data_ptr() for k, t in bufs.items()}, nbytes)
+        torch.cuda.synchronize()
+        n = nbytes // 4
+        return {"rc": rc, "message": msg, "workspace_bytes": nbytes, "sentinels_intact": bool((bufs["workspace"][n:] == SENTINEL).all()),
+                "workspace_written": bool((bufs["workspace"][:n] != SENTINEL).any()),
+                "other_spares_intact": all(bool((bufs[k][-64:] == SENTINEL).all()) for k in ("dqkv", "dbias")),
+                "dbias_same_bits": bool(torch.equal(_bits(bufs["dbias"][:-64]), _bits(got["dbias"].reshape(-1)))),
+                "dqkv_same_bits": bool(torch.equal(_bits(bufs["dqkv"][:-64]), _bits(got["dqkv"].reshape(-1))))}
+
+    def scatter_adds(self):
+        """aim_swin_bias_scatter ADDS: from a non-zero dtable of dyadic values, with 4 table rows that no index entry names
+        (they keep their bits) and ntable H no multiple of the 128-thread block.  The dense gradient is given exactly, so the
+        bound is the dtable bound's own fp32 sum term, 2 n_t u fold(|dense|), plus one rounding of start + sum."""
+        out, H = {}, 3
+        for name, index in (("window", relative_position_index(7)), ("temporal", t_relative_coords(16))):
+            g = torch.Generator().manual_seed(7900 + len(out))
+            SS, ntable = index.numel(), int(index.max()) + 1 + 4
+            dense = torch.randn((H, SS), generator=g).to(F32)
+            start = (torch.randint(-32, 33, (ntable, H), generator=g).double() / 8).to(F32)
+            buf = torch.full((ntable * H + 64,), SENTINEL, dtype=F32, device=self.dev)
+            dtable = buf[:ntable * H].view(ntable, H)
+            dtable.copy_(start)
+            S = int(math.isqrt(SS))
+            self.ops.swin_bias_scatter(dense.view(H, S, S).to(self.dev), index.to(torch.int32).to(self.dev), dtable)
+            torch.cuda.synchronize()
+            got = dtable.cpu()
+            cnt = torch.bincount(index, minlength=ntable).double()[:, None]
+            add = fold(dense.double().view(H, S, S), index, ntable)
+            ref = start.double() + add
+            e_sum = 2 * cnt * U24 * fold(dense.double().abs().view(H, S, S), index, ntable)
+            bound = e_sum + U24 * (ref.abs() + e_sum)
+            named = cnt[:, 0] > 0
+            out[name] = {"ratio": ratio(got[named], ref[named], bound[named]), "ntable_H": ntable * H, "unnamed_rows": int((~named).sum()),
+                         "unnamed_rows_keep_their_bits": bool(torch.equal(_bits(got[~named]), _bits(start[~named]))),
+                         "spare_intact": bool((buf[ntable * H:] == SENTINEL).all()), "start_nonzero": bool((start != 0).float().mean() > 0.9)}
+        return out
+
 
 def main(argv):
-    (path,) = argv
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from aim_amd import ops
     dev = torch.device("cuda")
     run = Runner(ops, dev)
     res = {"cases": {}}
+    if argv[0] == "--sweep":
+        import time
+        path, t0 = argv[1], time.time()
+        with torch.no_grad():
+            res["pointer_refusals"] = run.pointer_refusals()
+            res["scatter_adds"] = run.scatter_adds()
+            res["workspace_guard"] = run.workspace_guard(chunk_cases()[0])
+            for case in chunk_cases() + sweep_cases():
+                res["cases"][case.name] = run.run_case(case, extras=True)
+        res["seconds"] = time.time() - t0
+        with open(path, "w") as f:
+            json.dump(res, f)
+        return
+    (path,) = argv
     with torch.no_grad():
         res["refusals"] = run.refusals()
         for case in cases():
