@@ -2,7 +2,8 @@
 restatement of both with bounds.
 
 A plain module (no fixtures): `test_lowrank_gpu.py` runs every case on the kernels, `test_lowrank_cases_cpu.py` proves on the
-CPU that the comparison rejects the bugs it is meant to catch.
+CPU that the comparison rejects the bugs it is meant to catch.  Two tables: cases() (real widths, few sizes) and
+sweep_groups() (every r, every last-tile row count, the narrowest and the widest D, the rarer call forms).
 
   forward    H_g = bf16(X W1_g^T + b1_g)           Y_g = alpha X + H_g W2_g^T + b2_g       (fp32 form, G = 1: resid + the same)
   backward   dH_g = bf16(dY_g W2_g)                dX = bf16(alpha sum_g dY_g + sum_g dH_g W1_g)
@@ -22,7 +23,9 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from gemm_cases import BF16, F32, U8, U24, _digest, _pad_intact, _padded, ratio  # noqa: E402,F401
 
-ROWS = (1, 127, 129, 1029)          # one row; below / above two forward tiles of 64 (and four backward tiles of 32); 17 tiles
+# one row; one short of / one past a forward tile of 128 (two backward tiles of 64, four of 32); 8 forward tiles (16 / 32
+# backward tiles) and 5 rows
+ROWS = (1, 127, 129, 1029)
 WIDTHS = ((128, 32), (256, 8), (768, 192), (1024, 256))     # the tiny fixtures' width, the smallest r, ViT-B/16, ViT-L/14
 
 
@@ -35,6 +38,8 @@ class Case:
     G: int
     alpha: float
     seed: int = 0
+    bias: str = "both"          # both | b1 | b2 | none: the biases that are passed; the wrapper gets None for the rest
+    form: str = "std"           # std | y_y32 (G = 1: also y[0] and y32 from one call) | h1 (G = 3: also H of adapter 1 alone)
 
 
 def cases():
@@ -46,6 +51,51 @@ def cases():
                     out.append(Case(f"M{M}/D{D}/r{r}/G{G}/a{int(alpha)}", M, D, r, G, alpha, seed))
                     seed += 1
     return out
+
+
+SWEEP_M = 161                       # 128 + 33 forward rows; 2 x 64 + 33 and 5 x 32 + 1 in the two backward kernels
+SWEEP_R = tuple(range(8, 257, 8))
+SWEEP_D = (64, 192)                 # nk = 1 (the first product's ring never prefetches) and nk = 3
+# (D, r, G): forward and 64-row backward at their smallest; the 32-row backward with rk = 4 and a partial last chunk
+ROW_SWEEP = ((64, 8, 1), (64, 200, 3))
+ROW_SWEEP_M = tuple(range(1, 131))          # every last-tile row count of the 128-, 64- and 32-row workgroups, and two past
+FORMS_AT = (161, 192, 72)           # (M, D, r) of the call forms: rk = 2 with a partial chunk
+
+
+def _name(M, D, r, G, alpha, bias="both", form="std"):
+    tail = (f"/bias-{bias}" if bias != "both" else "") + (f"/{form}" if form != "std" else "")
+    return f"M{M}/D{D}/r{r}/G{G}/a{int(alpha)}" + tail
+
+
+def sweep_groups():
+    """{group: [Case]}: every r; every last-tile row count on the three instantiations; the widest D; the call forms that
+    cases() leaves out (a NULL b1 and / or b2, y[0] beside y32, H asked of one adapter of three)"""
+    out, seed = {}, [1000]
+
+    def add(group, M, D, r, G, alpha, **kw):
+        out.setdefault(group, []).append(Case(_name(M, D, r, G, alpha, **kw), M, D, r, G, float(alpha), seed[0], **kw))
+        seed[0] += 1
+
+    for G in (1, 3):
+        for D in SWEEP_D:
+            for r in SWEEP_R:                   # alpha alternates along r; the two widths of an (r, G) take the two values
+                add(f"r/G{G}/D{D}", SWEEP_M, D, r, G, 1 + (r // 8 + (D == SWEEP_D[1])) % 2)
+    for D, r, G in ROW_SWEEP:
+        for M in ROW_SWEEP_M:
+            add(f"rows/D{D}/r{r}/G{G}", M, D, r, G, 1)
+    add("wide", 129, 8192, 256, 3, 1)
+    add("wide", 129, 8192, 136, 1, 2)
+    M, D, r = FORMS_AT
+    for G in (1, 3):
+        for k, bias in enumerate(("b1", "b2", "none")):
+            add("forms", M, D, r, G, 1 + (k + G // 3) % 2, bias=bias)
+    add("forms", M, D, r, 1, 2, form="y_y32")
+    add("forms", M, D, r, 3, 1, form="h1")
+    return out
+
+
+def sweep_cases():
+    return [c for group in sweep_groups().values() for c in group]
 
 
 def make_inputs(c: Case) -> Dict[str, torch.Tensor]:
@@ -70,12 +120,16 @@ def dy_of(c: Case, inp, i: int):
     return inp["dY_buf"][:, i * c.D:(i + 1) * c.D]
 
 
-MUTANTS = ("alpha_other", "no_b1", "no_b2", "permuted", "h_unrounded", "dx_no_skip", "dx_one_dy")
+MUTANTS = ("alpha_other", "no_b1", "no_b2", "permuted", "h_unrounded", "dx_no_skip", "dx_one_dy", "r_tail", "d_last_step",
+           "bias_ignored_null")
 
 
 def mutants(c: Case):
-    on = {"alpha_other": True, "no_b1": True, "no_b2": True, "permuted": c.G == 3, "h_unrounded": True, "dx_no_skip": True,
-          "dx_one_dy": c.G == 3}
+    """r_tail: the second product leaves out the hidden units of the last, partial 64-chunk of r; d_last_step: the first
+    product leaves out the last 64 columns of D; bias_ignored_null: a bias that was not passed is added all the same"""
+    on = {"alpha_other": True, "no_b1": c.bias in ("both", "b1"), "no_b2": c.bias in ("both", "b2"), "permuted": c.G == 3,
+          "h_unrounded": True, "dx_no_skip": True, "dx_one_dy": c.G == 3, "r_tail": c.r % 64 != 0, "d_last_step": True,
+          "bias_ignored_null": c.bias != "both"}
     return [m for m in MUTANTS if on[m]]
 
 
@@ -85,14 +139,18 @@ def expected(c: Case, inp, got=None, mut: Optional[str] = None):
     X = x_of(c, inp).double()
     alpha = c.alpha if mut != "alpha_other" else 3.0 - c.alpha
     src = (lambda i: (i + 1) % c.G) if mut == "permuted" else (lambda i: i)       # output i computed with adapter src(i)
+    with_b1 = (c.bias in ("both", "b1") or mut == "bias_ignored_null") and mut != "no_b1"
+    with_b2 = (c.bias in ("both", "b2") or mut == "bias_ignored_null") and mut != "no_b2"
+    Dk = c.D - 64 if mut == "d_last_step" else c.D                  # the columns of D the first product sums over
+    ru = c.r // 64 * 64 if mut == "r_tail" else c.r                 # the hidden units the second product sums over
     out = {}
     for i in range(c.G):
         W1, b1 = inp[f"W1_{src(i)}"].double(), inp[f"b1_{src(i)}"].double()
-        ref = X @ W1.T + (0 if mut == "no_b1" else b1[None, :])
+        ref = X[:, :Dk] @ W1[:, :Dk].T + (b1[None, :] if with_b1 else 0)
         e = 2 * c.D * U24 * (X.abs() @ W1.abs().T)
         out[f"H{i}"] = (ref, U8 * ref.abs() + e + 2 * U24 * ref.abs())
         dY, W2 = dy_of(c, inp, i).double(), inp[f"W2_{i}"].double()
-        ref = dY @ W2
+        ref = dY[:, :Dk] @ W2[:Dk]
         e = 2 * c.D * U24 * (dY.abs() @ W2.abs())
         out[f"dH{i}"] = (ref, U8 * ref.abs() + e + 2 * U24 * ref.abs())
     if got is None:
@@ -102,8 +160,8 @@ def expected(c: Case, inp, got=None, mut: Optional[str] = None):
             continue
         H = got[f"H{i}"].double() if mut != "h_unrounded" else got["_H_exact"][i]
         W2, b2 = inp[f"W2_{src(i)}"].double(), inp[f"b2_{src(i)}"].double()
-        acc = H @ W2.T
-        b2v = torch.zeros_like(b2) if mut == "no_b2" else b2
+        acc = H[:, :ru] @ W2[:, :ru].T
+        b2v = b2 if with_b2 else torch.zeros_like(b2)
         ref = alpha * X + acc + b2v[None, :]
         e = 2 * c.r * U24 * (H.abs() @ W2.abs().T) + 4 * U24 * ((alpha * X).abs() + acc.abs() + b2v.abs()[None, :])
         out[f"Y{i}"] = (ref, U8 * ref.abs() + e)
@@ -116,7 +174,7 @@ def expected(c: Case, inp, got=None, mut: Optional[str] = None):
         acc, eacc = 0, 0
         for i in range(c.G):
             dH, W1 = got[f"dH{i}"].double(), inp[f"W1_{i}"].double()
-            acc = acc + dH @ W1
+            acc = acc + dH[:, :ru] @ W1[:ru]
             eacc = eacc + dH.abs() @ W1.abs()
         ref = (0 if mut == "dx_no_skip" else alpha * skip) + acc
         e = 2 * c.G * c.r * U24 * eacc + (c.G + 3) * U24 * (alpha * sum(d.abs() for d in dYs) + acc.abs())
@@ -144,21 +202,27 @@ def simulate(c: Case, inp, mut: Optional[str] = None):
 # ------------------------------------------------------------------ the kernels, every call form of one case ----------------
 def run_case(ops, c: Case, dev):
     """Both kernels on `c`: X row-strided, the Y_g as column slabs of one buffer (G = 3) or row-strided (G = 1), H stored and
-    not, the fp32 form with its residual (G = 1), every dY_g a slab; each call twice.  Every output lies in a NaN-filled buffer
-    with spare rows and columns.  -> dict(checks, pad, finite, same: rerun / H-NULL outputs with equal bits)."""
+    not, the fp32 form with its residual (G = 1), every dY_g a slab; each call twice; the biases that c.bias names (None for
+    the rest).  c.form adds one call: y_y32 writes y[0] and y32 together, h1 asks for the H of adapter 1 alone; their outputs
+    must have the bits of the calls above.  Every output lies in a NaN-filled buffer with spare rows and columns.
+    -> dict(checks, pad, finite, same: rerun / H-NULL / form outputs with equal bits)."""
     inp = {k: v.to(dev) for k, v in make_inputs(c).items()}
     M, D, r, G = c.M, c.D, c.r, c.G
     X = x_of(c, inp)
     w1 = [inp[f"W1_{i}"] for i in range(G)]
     w2 = [inp[f"W2_{i}"] for i in range(G)]
-    b1 = [inp[f"b1_{i}"] for i in range(G)]
-    b2 = [inp[f"b2_{i}"] for i in range(G)]
+    b1 = [inp[f"b1_{i}"] if c.bias in ("both", "b1") else None for i in range(G)]
+    b2 = [inp[f"b2_{i}"] if c.bias in ("both", "b2") else None for i in range(G)]
     w1t = [w.T.contiguous() for w in w1]
     w2t = [w.T.contiguous() for w in w2]
     rec = {"pad": {}, "finite": {}, "same": {}}
 
-    def forward(store_h: bool, f32_form: bool):
+    def forward(store_h, f32_form: bool, with_y: Optional[bool] = None):
+        """store_h: True, False, or the indices of the adapters whose H is asked for; with_y: y[g] passed (default: exactly
+        where y32 is not)"""
         got, bufs = {}, {}
+        with_y = (not f32_form) if with_y is None else with_y
+        stored = [i for i in range(G) if (store_h is True or (store_h is not False and i in store_h))]
         yv, ybuf = _padded(M, G * D, BF16, dev)
         ys = [yv[:, i * D:(i + 1) * D] for i in range(G)]
         hv, hbuf = _padded(M, G * r, BF16, dev)
@@ -167,15 +231,18 @@ def run_case(ops, c: Case, dev):
         if f32_form:
             got["Y32"], bufs["Y32"] = _padded(M, D, F32, dev)
             kw = dict(y32=got["Y32"], resid=inp["resid"])
-        ops.lowrank_fwd(X, w1, b1, w2, b2, h=hs if store_h else None, y=None if f32_form else ys, alpha=c.alpha, **kw)
-        if not f32_form:
+        ops.lowrank_fwd(X, w1, b1, w2, b2, h=[hs[i] if i in stored else None for i in range(G)] if stored else None,
+                        y=ys if with_y else None, alpha=c.alpha, **kw)
+        if with_y:
             for i in range(G):
                 got[f"Y{i}"] = ys[i]
             bufs["Y"] = (ybuf, G * D)
-        if store_h:
-            for i in range(G):
-                got[f"H{i}"] = hs[i]
+        for i in stored:
+            got[f"H{i}"] = hs[i]
+        if len(stored) == G:
             bufs["H"] = (hbuf, G * r)
+        elif stored:                            # the slabs that were not asked for must still hold their NaNs
+            bufs["H"] = (hbuf, stored)
         return got, bufs
 
     def backward():
@@ -192,7 +259,14 @@ def run_case(ops, c: Case, dev):
     def pads(tag, bufs):
         for k, b in bufs.items():
             buf, cols = b if isinstance(b, tuple) else (b, D)
-            rec["pad"][f"{tag}:{k}"] = _pad_intact(buf, M, cols)
+            if isinstance(cols, list):          # H slabs `cols` written, the others not: NaN everywhere else
+                bits = buf.view(torch.int16).clone()
+                fill = torch.full((1,), float("nan"), dtype=BF16).view(torch.int16).item()
+                for i in cols:
+                    bits[:M, i * r:(i + 1) * r] = fill
+                rec["pad"][f"{tag}:{k}"] = bool((bits == fill).all())
+            else:
+                rec["pad"][f"{tag}:{k}"] = _pad_intact(buf, M, cols)
 
     def same(a, b):
         return all(torch.equal(a[k].view(torch.int16 if a[k].dtype == BF16 else torch.int32),
@@ -211,6 +285,16 @@ def run_case(ops, c: Case, dev):
         rec["same"]["fwd32_rerun"] = same(g32, g32b)
         rec["same"]["fwd32_H"] = same({"H0": g32["H0"]}, got)
         got["Y32"] = g32["Y32"]
+    if c.form == "y_y32":
+        both, bboth = forward(True, True, with_y=True)
+        pads("fwd_y_y32", bboth)
+        rec["same"]["fwd_y_y32"] = same(both, got) and {"Y0", "Y32", "H0"} <= set(both)
+    elif c.form == "h1":
+        part, bpart = forward([1], False)
+        pads("fwd_h1", bpart)
+        rec["same"]["fwd_h1"] = same(part, got) and set(part) == {"Y0", "Y1", "Y2", "H1"}
+    else:
+        assert c.form == "std", c.form
     gb, bb = backward()
     gb2, _ = backward()
     pads("bwd", bb)

@@ -1,7 +1,8 @@
 """ViT_CLIP_ZEROI2V(linear_adapter=True) on the MI355X: the whole backbone against the real reference's stored outputs and
 autograd gradients (tests/golden/zeroi2v_linear_tiny_{a,b,c,d}.npz: separate and shared attention adapters, 8 / 16 / 32
 frames, with and without the temporal class token), at ViT-B's real shape against the fp32 restatement
-tests/zeroi2v_linear_ref.py (itself held to the fixtures by tests/test_zeroi2v_linear_cpu.py), merging, the requires_grad
+tests/zeroi2v_linear_ref.py (itself held to the fixtures by tests/test_zeroi2v_linear_cpu.py), the same at a small shape with
+the bottlenecks 8, 72, 136, 200 and 248 that no fixture has, merging, the requires_grad
 contract, and two FlatAdamW steps of the sthv2 recipe in a child process.
 
 Bounds: 1.5e-2 rel-L2 on the bf16 output and 2.5e-2 on every trainable gradient -- the project's bounds for bf16 against an
@@ -111,6 +112,48 @@ def test_real_shape_against_the_restatement():
     print(f"zeroi2v linear real shape: output {ey:.3e}, worst gradient {worst[1]:.3e} ({worst[0]})")
     assert ey <= OUT_BOUND, ey
     assert worst[1] <= GRAD_BOUND, sorted(errs.items(), key=lambda kv: -kv[1])[:8]
+
+
+@pytest.mark.parametrize("bottleneck,share", [(8, False), (72, True), (136, False), (200, False), (248, False)])
+def test_uncommon_bottlenecks_against_the_restatement(bottleneck, share):
+    """The bottlenecks no fixture has: the smallest (8), and one with a partial last 64-chunk per rk = 2, 3, 4 (72, 136, 200,
+    248; the last two take the 32-row backward of the q / k / v adapters).  Width 256, 4 heads, 2 layers, 8 frames of 32 x 32,
+    2 clips, with the temporal class token; reference = tests/zeroi2v_linear_ref.py in fp32 on the CPU; every call twice."""
+    import aim_amd
+    from oracle import vit_clip_oracle as O
+    D, H, L, T, B = 256, 4, 2, 8, 2
+    st = O.synth_state_dict(ZL.backbone_param_shapes(32, T, 16, D, L, True, share, bottleneck), seed=79)
+    for k in st:
+        if ("Attn_Adapter" in k or "MLP_Adapter" in k) and k.endswith(".weight"):
+            st[k] = st[k] * C.ADAPTER_SCALE
+    m = aim_amd.ViT_CLIP_ZEROI2V(32, T, 16, D, L, H, drop_path_rate=0.0, with_t_cls_token=True, share_adapter=share,
+                                 bottleneck=bottleneck, linear_adapter=True)
+    m.init_weights()
+    m.load_state_dict(st, strict=True)
+    m = m.to(DEV).eval()
+    gen = torch.Generator().manual_seed(10)
+    imgs = torch.randn((B, 3, T, 32, 32), generator=gen)
+    g = torch.randn((B, D, T, 1, 1), generator=gen)
+    names = sorted(n for n, p in m.named_parameters() if p.requires_grad)
+    assert len(names) == (20 if share else 28) * L + 3
+    byname = dict(m.named_parameters())
+    y = m(imgs.to(DEV))
+    grads = torch.autograd.grad(y, [byname[n] for n in names], g.to(DEV))
+    y2 = m(imgs.to(DEV))
+    grads2 = torch.autograd.grad(y2, [byname[n] for n in names], g.to(DEV))
+    sr = {k: v.clone().requires_grad_(k in names) for k, v in st.items()}
+    yr = ZL.backbone(imgs, sr, H, T, True, share)
+    gr = torch.autograd.grad(yr, [sr[n] for n in names], g)
+    errs = grad_errors(names, dict(zip(names, grads)), dict(zip(names, gr)))
+    ey = rel(y, yr.detach())
+    worst = max(errs.items(), key=lambda kv: kv[1])
+    print(f"zeroi2v linear bottleneck {bottleneck}{' shared' if share else ''}: output {ey:.3e}, "
+          f"worst gradient {worst[1]:.3e} ({worst[0]})")
+    assert ey <= OUT_BOUND, ey
+    assert worst[1] <= GRAD_BOUND, sorted(errs.items(), key=lambda kv: -kv[1])[:8]
+    assert torch.equal(y.detach(), y2.detach())
+    for n, a, b in zip(names, grads, grads2):
+        assert torch.equal(a, b), n
 
 
 @pytest.mark.parametrize("tag", C.TAGS)
