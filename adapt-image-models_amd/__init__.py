@@ -23,6 +23,7 @@ from .aim_flash_win import AIM_FLASH_WIN  # noqa: E402,F401
 from .aim_flash import AIM_FLASH  # noqa: E402,F401
 from .timesformer import TimeSformer  # noqa: E402,F401
 from .swin2d_adapter import SwinTransformer2D_Adapter  # noqa: E402,F401
+from .swin3d import SwinTransformer3D  # noqa: E402,F401
 from .recognizer import (CrossEntropyLoss, GPUNormalize, I3DHead, Recognizer3D,  # noqa: E402,F401
                          register_module_hooks, top_k_accuracy)
 
@@ -31,5 +32,5 @@ from .dist import DistOptimizerHook, FlatAdamW, build_optimizer  # noqa: E402,F4
 
 __all__ += ["DistOptimizerHook", "FlatAdamW", "build_optimizer", "BACKBONES", "HEADS", "LOSSES", "MODELS", "RECOGNIZERS", "Config", "Registry", "build_backbone",
             "build_from_cfg", "build_head", "build_loss", "build_model", "build_recognizer", "register_into_mmaction",
-            "ViT_CLIP", "AIM", "ViT_ImageNet", "ViT_CLIP_ZEROI2V", "AIM_FLASH_WIN", "AIM_FLASH", "TimeSformer", "SwinTransformer2D_Adapter", "Recognizer3D", "I3DHead", "CrossEntropyLoss", "GPUNormalize", "register_module_hooks",
+            "ViT_CLIP", "AIM", "ViT_ImageNet", "ViT_CLIP_ZEROI2V", "AIM_FLASH_WIN", "AIM_FLASH", "TimeSformer", "SwinTransformer2D_Adapter", "SwinTransformer3D", "Recognizer3D", "I3DHead", "CrossEntropyLoss", "GPUNormalize", "register_module_hooks",
             "top_k_accuracy", "BLENDINGS", "LabelSmoothing", "MixupBlending", "CutmixBlending"]

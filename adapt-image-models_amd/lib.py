@@ -147,9 +147,12 @@ SIGNATURES = {
     "aim_swin_tattn_bwd": [P, P, P, P, P, P, I, I, I, I, P, L, P],
     "aim_swin_attn_bwd_workspace_bytes": [I, I, I],
     "aim_swin_bias_scatter": [P, P, P, I, I, I, P],
+    "aim_swin3d_attn_fwd": [P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, P],
+    "aim_swin3d_attn_bwd": [P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, P, L, P],
+    "aim_swin3d_attn_bwd_workspace_bytes": [I, I, I, I, I, I, I, I, I, I],
 }
 
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 
 def load_library():

@@ -564,6 +564,46 @@ def swin_bias_scatter(dense, index, dtable):
                                                _stream()), "aim_swin_bias_scatter")
 
 
+def _swin3d_sizes(entry, named, rows, H, table, full):
+    """the sizes of the buffers the 3-D Swin attention entries share: ``named`` maps a name to (tensor, dtype, columns)"""
+    for n_, (t_, dt_, cols) in named.items():
+        _chk(t_, dt_, n_)
+        if not t_.is_contiguous() or t_.numel() != rows * cols:
+            raise ValueError(f"{entry}: {n_} must be contiguous with {rows * cols} elements, got {tuple(t_.shape)}")
+    _chk(table, F32, "table")
+    ntab = (2 * full[0] - 1) * (2 * full[1] - 1) * (2 * full[2] - 1)
+    if not table.is_contiguous() or tuple(table.shape) != (ntab, H):
+        raise ValueError(f"{entry}: table must be contiguous [{ntab}, {H}], got {tuple(table.shape)}")
+
+
+def swin3d_attn_fwd(qkv, table, out, lse, clips, D, G, H, window, shift, full_window):
+    """3-D Swin window attention (head width 32) on the fused qkv [clips*D*G*G, 96 H], rows (clip, d, y, x): softmax attention
+    inside the boxes that cut each axis at 0, s, s + w, ... (the reference's rolled, masked windows; masked pairs at weight
+    exactly 0) under the bias table [(2Wt-1)(2Wh-1)(2Ww-1), H] f32 of ``full_window``.  ``window`` is the effective window,
+    ``shift`` its shift.  out [rows, 32 H] bf16; lse [rows, H] f32 (base 2)."""
+    rows, C = clips * D * G * G, 32 * H
+    _swin3d_sizes("swin3d_attn_fwd", dict(qkv=(qkv, BF16, 3 * C), out=(out, BF16, C), lse=(lse, F32, H)), rows, H, table, full_window)
+    check(load_library().aim_swin3d_attn_fwd(qkv.data_ptr(), table.data_ptr(), out.data_ptr(), lse.data_ptr(), clips, D, G, H,
+                                             *window, *shift, *full_window, _stream()), "aim_swin3d_attn_fwd")
+
+
+def swin3d_attn_bwd(qkv, table, dout, lse, delta, dqkv, dtable, clips, D, G, H, window, shift, full_window):
+    """backward of swin3d_attn_fwd from d(out) and the forward's lse: writes delta [rows, H] f32 and dqkv [rows, 96 H] and,
+    unless None, ADDS the table gradient onto dtable [table, H] f32 (fixed-order sums: equal bits on every run)."""
+    rows, C = clips * D * G * G, 32 * H
+    _swin3d_sizes("swin3d_attn_bwd", dict(qkv=(qkv, BF16, 3 * C), dout=(dout, BF16, C), lse=(lse, F32, H), delta=(delta, F32, H),
+                                          dqkv=(dqkv, BF16, 3 * C)), rows, H, table, full_window)
+    _chk(dtable, F32, "dtable")
+    if dtable is not None and (not dtable.is_contiguous() or dtable.shape != table.shape):
+        raise ValueError("swin3d_attn_bwd: dtable must be contiguous with the shape of table")
+    lib = load_library()
+    nbytes = lib.aim_swin3d_attn_bwd_workspace_bytes(clips, D, G, H, *window, *shift) if dtable is not None else 0
+    ws = torch.empty((nbytes // 4,), dtype=F32, device=qkv.device) if nbytes else None
+    check(lib.aim_swin3d_attn_bwd(qkv.data_ptr(), table.data_ptr(), dout.data_ptr(), lse.data_ptr(), delta.data_ptr(),
+                                  dqkv.data_ptr(), _p(dtable), clips, D, G, H, *window, *shift, *full_window, _p(ws), nbytes,
+                                  _stream()), "aim_swin3d_attn_bwd")
+
+
 def attn_fwd_cls(qkv, out_cls, lse_cls, BT, N, H):
     """attn_fwd for the class query of every (frame, head) alone: out_cls [BT, D], lse_cls [BT, H]."""
     _chk(qkv, BF16, "qkv"); _chk(out_cls, BF16, "out_cls"); _chk(lse_cls, F32, "lse_cls")

@@ -149,6 +149,8 @@ def register_into_mmaction() -> bool:
     MB.register_module(name="TimeSformer", force=True, module=TimeSformer)                 # timesformer.py:86
     from .swin2d_adapter import SwinTransformer2D_Adapter
     MB.register_module(name="SwinTransformer2D_Adapter", force=True, module=SwinTransformer2D_Adapter)      # swin2d_adapter.py:600
+    from .swin3d import SwinTransformer3D
+    MB.register_module(name="SwinTransformer3D", force=True, module=SwinTransformer3D)      # swin_transformer.py:458
     return True
 
 

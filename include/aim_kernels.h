@@ -32,7 +32,7 @@ extern "C" {
 
 typedef uint16_t aim_bf16;
 
-#define AIM_ABI_VERSION 18
+#define AIM_ABI_VERSION 19
 
 int aim_version(void);                /* == AIM_ABI_VERSION */
 const char* aim_last_error(void);     /* message of the last failing call on this thread */
@@ -654,6 +654,31 @@ int aim_swin_tattn_bwd(const aim_bf16* qkv, const float* bias, const aim_bf16* d
                        void* stream);
 int64_t aim_swin_attn_bwd_workspace_bytes(int sequences, int H, int S);
 int aim_swin_bias_scatter(const float* dense, const int* index, float* dtable, int H, int SS, int ntable, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * SwinTransformer3D (reference swin_transformer.py; ABI 19): attention at head width 32 inside 3-D windows under the learned
+ * 3-D relative-position bias, on the fused qkv [rows, 3 C] bf16 (C = 32 H, rows (clip, d, y, x) of a (D, G, G) token grid, no
+ * class row).  (wt, wh, ww) is the effective window (after the reference's get_window_size), (st, sh, sw) the shift and
+ * (Wt, Wh, Ww) the full window of the constructor, which gives the strides of table [(2Wt-1)(2Wh-1)(2Ww-1), H] f32.
+ * A sequence is one box of the partition that cuts each axis at 0, s, s + w, ... (0, w, 2w, ... where the shift is 0): the
+ * reference's roll, window_partition, -100 mask and their inverses, a masked pair having the weight exactly 0.  The bias of
+ * (query, key) is table[f(q) - f(k) + f(Wt-1, Wh-1, Ww-1)][h], f(t, h, w) = (t (2Wh-1) + h)(2Ww-1) + w.
+ * Capacity: wt wh ww <= 1024 tokens per window and at most 5248 table entries; (16,7,7) has 784 and 5239.
+ * fwd writes out [rows, C] bf16 and lse [rows, H] f32 (base 2).  bwd (from qkv, dout [rows, C] and the forward's lse) writes
+ * delta [rows, H] f32 (sum_j p_j dP_j), dqkv [rows, 3 C] bf16 (all three parts of every row) and, where dtable is not NULL,
+ * ADDS the table gradient (sum of the unrounded fp32 dS, no scale factor) onto dtable [table, H]: dense per-walk partial sums
+ * in the workspace, added in a fixed order (no atomics; equal bits on every run; dqkv does not depend on dtable being asked for).
+ * The 32^-1/2 scale is applied to the fp32 score; p and dS are rounded to bf16 as MFMA operands only.
+ * Refused before any launch: a window that does not divide D or G, a shift outside [0, w) or non-zero on an axis its window
+ * spans, a full window smaller than the effective one, more tokens or table entries than the capacity, rows that overflow
+ * 32-bit offsets, null pointers, bf16 buffers off 16 bytes or fp32 buffers off 4, a short workspace.
+ * ------------------------------------------------------------------------------------------ */
+int aim_swin3d_attn_fwd(const aim_bf16* qkv, const float* table, aim_bf16* out, float* lse, int clips, int D, int G, int H, int wt,
+                        int wh, int ww, int st, int sh, int sw, int Wt, int Wh, int Ww, void* stream);
+int aim_swin3d_attn_bwd(const aim_bf16* qkv, const float* table, const aim_bf16* dout, const float* lse, float* delta,
+                        aim_bf16* dqkv, float* dtable, int clips, int D, int G, int H, int wt, int wh, int ww, int st, int sh,
+                        int sw, int Wt, int Wh, int Ww, float* workspace, int64_t workspace_bytes, void* stream);
+int64_t aim_swin3d_attn_bwd_workspace_bytes(int clips, int D, int G, int H, int wt, int wh, int ww, int st, int sh, int sw);
 
 #ifdef __cplusplus
 }
